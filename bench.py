@@ -1,6 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X DCT codec hot path (BASELINE.json `metric`).
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what the headline
+figure needs: it sets up the workload, runs W untimed steps, times K steps
+(K1's launches event-stamped for `roofline`, as always), checks every codec
+context's device status, and prints the result line (`value`, `ms_per_step` =
+wall time of the timed region / K, in milliseconds).  --dump-outputs DIR then
+also writes what the last timed step computed (Run.dump_outputs: stream sizes,
+the first stream, seeded samples of every stream and of the decoded frames) as
+float32 / float64 DIR/<name>.npy; the inputs are the same in every run, so two
+builds can be compared file by file.  Everything else described below (the
+checks of the first pass, of the timed region's outputs and of the gathered
+streams; the per-kernel breakdown pass with roofline_isolated,
+roofline_decode_isolated and kernel_us; cpu_baseline; side) runs only with
+--full, and those fields are null (`verified`: empty) without it.
+
 Workloads (--workload; `auto`, the default, is chef-big at every rank count,
 so the driver's 1/2/4/8-GPU runs form one weak-scaling curve of one workload):
   chef-big  BASELINE.json configs[1], the metric's own configuration: a step
@@ -109,6 +123,9 @@ MANIFEST_4K = os.path.join(ROOT, "tests", "golden", "batch4k_512.json")
 BIG_DECODED_SHA = "5e7769191188285cc127c6b4da900b3420f064191f707383c82128c14e497e5c"
 BIG_RECOMPRESSED_SHA = "fe9b7317653c2b44a9f24436f0e349b083b4e368cf9653e8777e9f7a79cebfcc"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table (8 TB/s spec)
+# chef-big at N = 1: up to the default 40 steps every step has payload slots of its own (45.8 MB each);
+# longer runs reuse those 40 steps' worth in turn
+SLOT_RING_STEPS = 40
 SLOT_4K = 4 << 20  # batch4k payload slot: the largest of the 512 streams is 2,471,404 B (capacity is checked on device)
 # K1's VALU issue time: the fast path's loop body in the
 # gfx950 code object of this build, weighted by the issue cost of each
@@ -135,6 +152,11 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=40,
                     help="timed steps; chef-big: --inflight x --batch frames per rank, batch4k: the --frames batch")
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also check the outputs (first pass, timed region, gathered streams) and run the other "
+                         "measurements: per-kernel breakdown, isolated rooflines, cpu_baseline, side")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy")
     ap.add_argument("--workload", choices=("auto", "chef-big", "batch4k"), default="auto",
                     help="auto: chef-big (configs[1]) at every rank count (side.batch4k runs configs[3])")
     ap.add_argument("--frames", type=int, default=512,
@@ -576,7 +598,11 @@ class Run:
 
     def alloc_slots(self, steps, warmup):
         if self.name == "chef-big":
-            nslot = max(steps * self.per_step, self.per_step * max(1, warmup))
+            # (N = 1: a ring of at most SLOT_RING_STEPS steps' slots, so any
+            # --steps fits in HBM; a slot comes back to the context and stream
+            # that wrote it last, since the ring holds whole steps)
+            nsteps = max(steps, warmup, 1)
+            nslot = self.per_step * (min(nsteps, SLOT_RING_STEPS) if self.world == 1 else nsteps)
         else:
             # (N > 1: one slot set per step, the gather reads them after the
             # step's launches; N = 1: one set, reused in stream order)
@@ -616,13 +642,21 @@ class Run:
         self.codec.decompress(k, self.d_pay[slot:slot + nb], self.d_size[slot:slot + nb], self.cap, nb, self.w,
                               self.h, self.q3, self.d_out[k])
 
-    def warmup(self, passes):
-        """passes x one step, untimed; the first pass is checked: chef-big,
-        every stream against the pinned reference bytes and every round trip
-        against the host-API decode (GPU); batch4k, group by group, every
-        stream and its decode against the manifest."""
+    def warmup(self, passes, check=True):
+        """passes x one step, untimed; with `check` (--full) the first pass is
+        checked: chef-big, every stream against the pinned reference bytes and
+        every round trip against the host-API decode (GPU); batch4k, group by
+        group, every stream and its decode against the manifest."""
         c = self.codec
         n = max(1, passes) * self.ngroups
+        self.want_decode = None
+        if not check:
+            for j in range(n):
+                self.run_group(j)
+            c.check()
+            if self.name == "chef-big":
+                self.payload0 = int(self.d_size[0].item())
+            return
         if self.name == "batch4k":
             for j in range(self.ngroups):
                 k, nb, slot = self.run_group(j)
@@ -758,6 +792,53 @@ class Run:
                                          f"{nstream} streams == {src}; {ndec} frames of each context's last "
                                          f"decode == " + ("the manifest" if self.name == "batch4k"
                                                           else "the host-API decode"))
+
+    def dump_outputs(self, steps, path, seed=0):
+        """--dump-outputs: what the last timed step left for its caller, as
+        float32 / float64 .npy files under `path` (rank r > 0 appends _rank<r>
+        to the names), about 40 MB at the default shape:
+          stream_sizes    [n] the step's stream sizes in bytes, frame order
+          stream_first    the first frame's whole stream
+          stream_samples  [n, S] every stream's bytes at S fixed relative
+                          positions (floor(u_i * size), u seeded)
+          decoded_samples [m, D] the decoded frames still in the output
+                          buffers (each context's last launch group of the
+                          step, in launch order) at D fixed seeded offsets
+        The positions depend only on `seed` and the shapes, so two builds run
+        with the same arguments write comparable files."""
+        import numpy as np
+        torch = self.codec.torch
+        self.codec.sync()
+        rng = np.random.default_rng(seed)
+        js = range((steps - 1) * self.ngroups, steps * self.ngroups)
+        n = sum(self.group_desc(j)[2] for j in js)
+        S = max(1, min(16384, (2 << 20) // n))
+        u = torch.from_numpy(rng.random(S)).to(self.d_pay.device)
+        sizes, samples, first = [], [], None
+        for j in js:
+            _, _, nb, slot = self.group_desc(j)
+            sz = self.d_size[slot:slot + nb].to(torch.float64).clamp(0, self.cap)
+            pos = (u[None, :] * sz[:, None]).floor().to(torch.int64).clamp_(max=self.cap - 1)
+            samples.append(torch.gather(self.d_pay[slot:slot + nb], 1, pos).to(torch.float32).cpu())
+            sizes.append(self.d_size[slot:slot + nb].to(torch.float64).cpu())
+            if first is None:
+                n0 = min(max(int(self.d_size[slot].item()), 0), self.cap)
+                first = self.d_pay[slot, :n0].to(torch.float32).cpu()
+        last = {}
+        for j in js:
+            last[self.group_desc(j)[0]] = j
+        m = sum(self.group_desc(j)[2] for j in last.values())
+        D = max(1, min(32768, (4 << 20) // m, self.samples))
+        off = torch.from_numpy(np.sort(rng.choice(self.samples, D, replace=False))).to(self.d_out.device)
+        decs = []
+        for j, k in sorted((j, k) for k, j in last.items()):
+            nb = self.group_desc(j)[2]
+            decs.append(self.d_out[k, :nb * self.samples].view(nb, self.samples)[:, off].to(torch.float32).cpu())
+        os.makedirs(path, exist_ok=True)
+        tag = f"_rank{self.rank}" if self.rank else ""
+        for name, t in (("stream_sizes", torch.cat(sizes)), ("stream_first", first),
+                        ("stream_samples", torch.cat(samples)), ("decoded_samples", torch.cat(decs))):
+            np.save(os.path.join(path, f"{name}{tag}.npy"), t.numpy())
 
     def verify_gathered(self, got, steps):
         """Rank 0, N > 1: the gathered streams in global frame order."""
@@ -973,7 +1054,7 @@ def main(argv=None):
 
     run = Run(name, codec, raw, big, args, world, rank)
     run.alloc_slots(args.steps, args.warmup)
-    checked(run.warmup, "the untimed pass", dist, world, rank, dev, args.warmup)
+    checked(run.warmup, "the untimed pass", dist, world, rank, dev, args.warmup, args.full)
 
     # ---- timed region: K1 (the roofline kernel) event-stamped on every launch
     # group (the average is over the launches a rocprofv3 kernel trace of this
@@ -986,7 +1067,12 @@ def main(argv=None):
             c.profile(True, kernels=["fdct_quant", "fdct_fix"])
     t, got = run.timed(args.steps, dist, dev, args.gather_chunk)
     checked(codec.check, "the timed region", dist, world, rank, dev, bad_ranks=run.gather_bad)
-    checked(run.verify_timed, "the timed region's outputs", dist, world, rank, dev, args.steps)
+    if args.dump_outputs:
+        run.dump_outputs(args.steps, args.dump_outputs)
+    # everything below but K1's stamps and the result line is --full's
+    full = args.full
+    if full:
+        checked(run.verify_timed, "the timed region's outputs", dist, world, rank, dev, args.steps)
     stats = {}
     for c in stamped:
         for kname, (kms, kn) in c.kernel_stats().items():
@@ -1001,12 +1087,12 @@ def main(argv=None):
     if world > 1:
         ranks = rank_timings(dist, world, dev, run.timing)
         t = max(r["wall_s"] for r in ranks)
-        if rank == 0:
+        if rank == 0 and full:
             run.verified["gathered"] = run.verify_gathered(got, args.steps)
     # per-kernel breakdown (all kernels stamped, one launch group at a time on
     # context 0), outside the timed region
     breakdown = {}
-    if gpu and args.breakdown_steps > 0:
+    if full and gpu and args.breakdown_steps > 0:
         c0 = codec.codecs[0]
         c0.profile(True)
         for i in range(args.breakdown_steps):
@@ -1016,11 +1102,11 @@ def main(argv=None):
         c0.profile(False)
     side = None
     b4 = None
-    if gpu and not args.no_side and name == "chef-big" and run.q == 50:
+    if full and gpu and not args.no_side and name == "chef-big" and run.q == 50:
         # configs[3]/[4] on every rank (all ranks take part in its gather),
         # before rank 0's own side work so no rank waits in a collective for it
         b4 = batch4k_side(args, codec, raw, big, world, rank, dist, dev)
-    if gpu and rank == 0 and not args.no_side:
+    if full and gpu and rank == 0 and not args.no_side:
         side = side_measurements(args, run, codec, raw, big, world, dev)
         if b4 is not None:
             side["batch4k"] = b4
@@ -1055,7 +1141,7 @@ def main(argv=None):
         for k, us in kernel_us.items():
             log(f"kernel {k:16s} {us:9.2f} us/launch")
         cpu = None
-        if gpu and world == 1 and args.cpu_seconds > 0:
+        if full and gpu and world == 1 and args.cpu_seconds > 0:
             crow = raw if name == "chef-big" else bytes(run.d_in[0].cpu().numpy())
             cpu = cpu_baseline(crow, run.w, run.h, run.q, args.cpu_seconds, args.cpu_threads)
         if name == "chef-big":
@@ -1072,7 +1158,7 @@ def main(argv=None):
         line = {
             "metric": "megapixels/sec DCT compress+decompress, 4K IYUV; achieved HBM GB/s vs peak",
             "value": round(value, 2), "unit": "MP/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(t / args.steps * 1e3, 4), "higher_is_better": True,
+            "warmup": args.warmup, "full": full, "ms_per_step": round(t / args.steps * 1e3, 4), "higher_is_better": True,
             "scaling": run.scaling, "vs_baseline": None, "dtype": "u8/int16 (fp32 transform)",
             "data": data,
             "config": {"workload": workload, "frame": f"{run.w}x{run.h}", "quality": run.q,

@@ -189,7 +189,7 @@ def test_bench_n2_loop_cpu_codec(workload, extra):
     tests/golden/batch4k_512.json; chef-big: the pinned reference bytes)."""
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-codec",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-codec", "--full",
                         "--workload", workload, "--warmup", "1"] + extra,
                        capture_output=True, text=True, timeout=600, env=_bench_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -213,6 +213,52 @@ def test_bench_n2_loop_cpu_codec(workload, extra):
     assert ranks[1]["gather_bytes"] > 0 and ranks[0]["gather_bytes"] == ranks[1]["gather_bytes"]
     assert d["gather"]["bytes_to_rank0"] == ranks[1]["gather_bytes"]
     assert abs(d["ms_per_step"] * steps / 1e3 - max(r["wall_s"] for r in ranks)) < 1e-3
+
+
+def test_bench_plain_and_full_dump_the_same_outputs(tmp_path):
+    """A plain run (no --full) times --steps steps, checks nothing and leaves
+    the --full fields empty; --dump-outputs writes the last step's outputs as
+    float .npy files, identical from run to run and with --full, and the first
+    stream they hold is the pinned reference stream."""
+    import hashlib
+    import importlib.util
+    import subprocess
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    lines, dumps = [], []
+    for tag, extra in (("plain", []), ("full", ["--full"])):
+        out = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cpu-codec",
+                            "--warmup", "1", "--batch", "1", "--inflight", "2", "--steps", "3", "--input-frames", "2",
+                            "--dump-outputs", str(out)] + extra,
+                           capture_output=True, text=True, timeout=600, env=_bench_env(), cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_bench_json(r.stdout))
+        dumps.append({p.stem: np.load(p) for p in sorted(out.glob("*.npy"))})
+    plain, full = lines
+    for d in lines:
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "MP/s" and d["higher_is_better"] is True
+        # value = MP of the timed frames / the time of the timed steps
+        mp = 3 * d["config"]["frames_per_step"] * 4032 * 3008 / 1e6
+        assert abs(d["value"] - mp / (3 * d["ms_per_step"] / 1e3)) <= 1e-3 * d["value"]
+    assert plain["full"] is False and not plain["verified"]
+    assert full["full"] is True and "first_pass" in full["verified"]
+    assert full["verified"]["timed_region"].startswith("timed-region outputs checked")
+    assert set(dumps[0]) == {"stream_sizes", "stream_first", "stream_samples", "decoded_samples"}
+    total = 0
+    for name, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, name
+        assert np.array_equal(a, dumps[1][name]), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    sizes = dumps[0]["stream_sizes"]
+    assert sizes.shape == (2,) and (sizes == plain["config"]["payload_bytes"]).all()
+    first = dumps[0]["stream_first"]
+    assert len(first) == sizes[0]
+    assert hashlib.sha256(first.astype(np.uint8).tobytes()).hexdigest() == bench.BIG_RECOMPRESSED_SHA
+    assert dumps[0]["stream_samples"].shape[0] == 2 and dumps[0]["decoded_samples"].shape[0] == 2
 
 
 def test_bench_auto_workload_is_one_curve():

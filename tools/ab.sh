@@ -8,5 +8,5 @@ OUT=$R/gpurun_out/ab_$TAG
 mkdir -p $OUT
 for d in "$@"; do
   n=$(basename $d)
-  MYYUV_HIP_LIB=$d/libmyyuv_hip.so timeout -k 10 120 python3 $R/bench.py --steps 30 --warmup 5 --cpu-seconds 0 > $OUT/$n.json 2> $OUT/$n.err || exit 1
+  MYYUV_HIP_LIB=$d/libmyyuv_hip.so timeout -k 10 120 python3 $R/bench.py --full --steps 30 --warmup 5 --cpu-seconds 0 > $OUT/$n.json 2> $OUT/$n.err || exit 1
 done

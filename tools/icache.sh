@@ -8,5 +8,5 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for d in "$@"; do
   n=$(basename $d)
-  MYYUV_HIP_LIB=$R/$d/libmyyuv_hip.so timeout -k 10 200 rocprofv3 --pmc SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQC_ICACHE_REQ SQC_TC_INST_REQ SQ_IFETCH_LEVEL SQ_WAVE_CYCLES SQ_WAIT_INST_ANY -d $OUT/$n -o run --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --cpu-seconds 0 --no-kernel-events > $OUT/$n.json 2> $OUT/$n.err || exit 1
+  MYYUV_HIP_LIB=$R/$d/libmyyuv_hip.so timeout -k 10 200 rocprofv3 --pmc SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQC_ICACHE_REQ SQC_TC_INST_REQ SQ_IFETCH_LEVEL SQ_WAVE_CYCLES SQ_WAIT_INST_ANY -d $OUT/$n -o run --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 --no-kernel-events > $OUT/$n.json 2> $OUT/$n.err || exit 1
 done
