@@ -108,3 +108,69 @@ def test_host_batch_capacity(codec, golden):
     assert rc == myyuv_hip.E_CAPACITY
     assert sizes[0] == len(golden("chef-with-trumpet-DCT-50.myyuv").data)
     assert not out.any()  # nothing was written into a slot too small for it
+
+
+def test_context_lifecycle(oracle, golden):
+    """Contexts closed in every state they can be in: the pipeline never
+    built, idle behind single frames, behind batches of one and of several
+    chunks per slot, and straight after a batch that failed; and one created
+    after others were destroyed.  Every result still equals the oracle's."""
+    import malformed
+    import myyuv_hip
+    w, h, q = 256, 128, (60, 50, 90)
+    frames = _frames(golden, 9)
+    pays = [oracle.compress(f, w, h, q) for f in frames]
+    dec = [oracle.decompress(p, w, h, q) for p in pays]
+
+    myyuv_hip.Codec(0).close()  # (1) nothing ever ran
+
+    def single(c, _style):
+        assert c.compress(frames[0], w, h, q) == pays[0]
+        assert c.decompress(pays[0], w, h, q) == dec[0]
+
+    def batch(n):
+        def run(c, style):
+            assert getattr(c, "compress_" + style)(frames[:n], w, h, q) == pays[:n]
+            assert getattr(c, "decompress_" + style)(pays[:n], w, h, q) == dec[:n]
+        return run
+
+    for style in ("batch", "frames"):  # (2) closed behind each kind of call
+        for run in (single, batch(2), batch(9)):
+            c = myyuv_hip.Codec(0)
+            try:
+                run(c, style)
+            finally:
+                c.close()
+
+    # (3) closed straight after a failed batch (the case of
+    # test_host_batch_decode_error_names_the_block)
+    g = golden("chef-with-trumpet-DCT-50.myyuv")
+    gw, gh, gq = g.width, g.height, tuple(g.params)
+    nblk = (gw // 8) * (gh // 8) + 2 * (gw // 16) * (gh // 16)
+    _, badpay = next((nm, p) for nm, p, kind in malformed.cases(g.data) if nm == "bad_code")
+    with pytest.raises(RuntimeError) as ref:
+        oracle.decompress(badpay, gw, gh, gq)
+    c = myyuv_hip.Codec(0)
+    try:
+        with pytest.raises(myyuv_hip.CodecError) as one:
+            c.decompress(badpay, gw, gh, gq)
+    finally:
+        c.close()
+    assert one.value.code == ref.value.args[0] and one.value.bad_block >= 0
+    bad = [g.data] * 20
+    bad[13] = badpay
+    for style in ("batch", "frames"):
+        c = myyuv_hip.Codec(0)
+        try:
+            with pytest.raises(myyuv_hip.CodecError) as e:
+                getattr(c, "decompress_" + style)(bad, gw, gh, gq)
+        finally:
+            c.close()
+        assert e.value.code == one.value.code
+        assert e.value.bad_block == 13 * nblk + one.value.bad_block
+
+    c = myyuv_hip.Codec(0)  # (4) a context created after all those were destroyed
+    try:
+        batch(2)(c, "batch")
+    finally:
+        c.close()

@@ -14,7 +14,9 @@ objs=""
 for k in k_transform k_huff_encode k_huff_decode k_stream k_color; do
   /opt/rocm/bin/hipcc $F -c $C/$k.hip -o $out/$k.o & objs="$objs $out/$k.o"
 done
-/opt/rocm/bin/hipcc $F -x hip -c $C/myyuv_hip.cpp -o $out/myyuv_hip.o & objs="$objs $out/myyuv_hip.o"
+for k in myyuv_hip myyuv_hip_diag; do
+  /opt/rocm/bin/hipcc $F -x hip -c $C/$k.cpp -o $out/$k.o & objs="$objs $out/$k.o"
+done
 wait
 /opt/rocm/bin/hipcc --offload-arch=${ARCH:-gfx950} -fgpu-rdc --hip-link -shared -mllvm -vectorize-slp=false ${LINKFLAGS:-} -o $out/libmyyuv_hip.so $objs
 rm -f $out/*.o

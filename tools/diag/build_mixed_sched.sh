@@ -13,7 +13,9 @@ for k in k_transform k_huff_encode k_huff_decode k_stream k_color; do
   X=""; [ "$k" = "$ff" ] && X="-mllvm -amdgpu-sched-strategy=iterative-minreg"
   /opt/rocm/bin/hipcc $F $X -c $C/$k.hip -o $out/$k.o & objs="$objs $out/$k.o"
 done
-/opt/rocm/bin/hipcc $F -x hip -c $C/myyuv_hip.cpp -o $out/myyuv_hip.o & objs="$objs $out/myyuv_hip.o"
+for k in myyuv_hip myyuv_hip_diag; do
+  /opt/rocm/bin/hipcc $F -x hip -c $C/$k.cpp -o $out/$k.o & objs="$objs $out/$k.o"
+done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $out/libmyyuv_hip.so $objs
 rm -f $out/*.o

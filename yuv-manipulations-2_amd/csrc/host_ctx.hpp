@@ -1,0 +1,271 @@
+// host_ctx.hpp — what the two host translation units share: the kernels'
+// declarations, the owners of HIP resources, the context, and the pieces every
+// entry point is made of (myyuv_hip.cpp: the product; myyuv_hip_diag.cpp: the
+// diagnostic and known-answer entry points).
+#pragma once
+#include <hip/hip_ext.h>
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "codec_common.hpp"
+#include "k_chain.hpp"
+#include "k_stream.hpp"
+#include "myyuv_hip.h"
+
+namespace myyuv_gpu {
+__global__ void k_fdct_quant(const uint8_t*, FrameGeom, const QTables*, uint4*, uint8_t*, uint32_t*, uint4*,
+                             uint32_t*, uint32_t*, uint32_t);
+__global__ void k_fdct_fix(const uint8_t*, FrameGeom, const QTables*, uint4*, uint8_t*, uint32_t*, uint4*,
+                           uint32_t*, uint32_t);
+__global__ void k_dequant_idct(const uint4*, const uint8_t*, const uint4*, FrameGeom, const QTables*, uint8_t*,
+                               uint4*);
+__global__ void k_decode_idct(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
+                              const uint32_t*, FrameGeom, uint32_t, uint32_t, const QTables*, uint4*, uint8_t*,
+                              unsigned long long*);
+template <uint32_t W>
+__global__ void k_huff_encode(const uint4*, const uint32_t*, const uint4*, FrameGeom, uint32_t*, uint32_t*,
+                              uint8_t*, uint32_t*, uint32_t*, uint32_t*);
+__global__ void k_huff_encode_wave(const uint4*, const uint8_t*, FrameGeom, uint32_t*, uint8_t*, uint32_t*,
+                                   const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t,
+                                   uint32_t);
+__global__ void k_huff_encode_wide(const uint4*, const uint8_t*, const uint4*, FrameGeom, uint32_t*, uint8_t*,
+                                   uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*,
+                                   uint32_t, uint32_t);
+__global__ void k_huff_encode_r16(const uint4*, const uint8_t*, const uint4*, FrameGeom, uint32_t*, uint8_t*,
+                                  uint32_t*, const uint32_t*, const uint32_t*, uint32_t*, uint32_t*, uint32_t);
+__global__ void k_encode_tile(const uint8_t*, FrameGeom, const QTables*, uint4*, uint8_t*, uint32_t*, uint32_t*,
+                              uint8_t*, uint32_t*, uint32_t*, uint32_t*);
+__global__ void k_tile_scan(uint32_t*, FrameGeom, uint8_t*, uint32_t, uint32_t*, unsigned long long*);
+__global__ void k_scan_chain(const uint8_t*, uint32_t, ScanSrc, const uint32_t*, uint32_t, FrameGeom,
+                             StreamDesc*, uint32_t*, uint32_t*, uint32_t, unsigned long long*,
+                             uint32_t, unsigned long long*);
+__global__ void k_stream_out(const uint32_t*, const uint32_t*, const uint8_t*, const uint32_t*,
+                             const uint32_t*, FrameGeom, uint8_t*, uint32_t, uint32_t);
+__global__ void k_huff_decode(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
+                              const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t,
+                              uint4*, uint8_t*, unsigned long long*);
+template <int BPP>
+__global__ void k_bmp_to_iyuv(const uint8_t*, uint32_t, uint32_t, uint32_t, uint8_t*);
+}  // namespace myyuv_gpu
+
+using namespace myyuv_gpu;
+
+// (nothing below is part of the library's ABI)
+#pragma GCC visibility push(hidden)
+
+// A HIP handle that is released with its owner (move-only).
+template <class T, hipError_t (*Release)(T)>
+struct Owned {
+  T h = nullptr;
+  Owned() = default;
+  Owned(Owned&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+  Owned& operator=(Owned&& o) noexcept {
+    std::swap(h, o.h);
+    return *this;
+  }
+  ~Owned() {
+    if (h) (void)Release(h);
+  }
+  operator T() const { return h; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Pinned = Owned<void*, hipHostFree>;
+
+// A device buffer that only grows (its content is lost when it does).
+struct DevBuf {
+  void* p = nullptr;
+  size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  int grow(size_t want) {
+    if (want <= n) return 0;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+    if (hipMalloc(&p, want) != hipSuccess) return MYYUV_E_HIP;
+    n = want;
+    return 0;
+  }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+
+constexpr uint32_t kPipeMaxChunk = 8;
+
+// The host-buffer batch pipeline (myyuv_hip.cpp, pipe_frames): H2D on cin,
+// kernels on the context's stream, D2H on cout; two slots of up to
+// kPipeMaxChunk frames.  (The streams first: they outlive what runs on them.)
+struct HostPipe {
+  Stream cin, cout;
+  Event pev[3][2];  // [copied in, computed, copied out][slot]
+  DevBuf pin[2], pout[2], psz[2], perr[2];
+  Pinned hsz;   // 2 x kPipeMaxChunk u32 sizes
+  Pinned herr;  // 2 error words
+  uint32_t* sizes(uint32_t slot) const { return static_cast<uint32_t*>(hsz.h) + slot * kPipeMaxChunk; }
+  unsigned long long* err(uint32_t slot) const { return static_cast<unsigned long long*>(herr.h) + slot; }
+};
+
+// (Members are destroyed in reverse order: everything after `stream` goes
+// before it.)
+struct myyuv_hip_ctx {
+  int device = 0;
+  Stream stream;
+  // One context's scratch buffers (coef, slots, sizes, scan status words ...)
+  // serve one call at a time: every entry point records `done` on its stream
+  // and a call on another stream first waits for it (StreamOrder), so calls
+  // on different streams through one context run in call order.
+  Event done;
+  hipStream_t last_stream = nullptr;
+  DevBuf frame, coef, sizes, loff, tiles, payload, err, psize, desc, work, qtd;
+  DevBuf stage, oslots, tinfo, srcoff;  // K2 -> K4 (codec_common.hpp)
+  DevBuf bmp;   // staged BMP pixels (host-buffer BMP -> IYUV)
+  DevBuf rmask; // per block: bit c = coefficient row c nonzero (K1 -> overflow passes, K5 -> K6)
+  DevBuf binfo; // per block: K1 -> K2's classification (binfo_word, codec_common.hpp)
+  DevBuf zq;    // 256 zero bytes: K6's source for rows the mask says are zero
+  DevBuf sink;  // K1/K6 stores of lanes past a plane's end (128 x 16 B, never read)
+  // K1 -> k_fdct_fix: the unproven units' lists and counts (fix_count /
+  // fix_list, codec_common.hpp; fix_par alternates from launch to launch)
+  DevBuf fix;
+  uint32_t fix_par = 0;
+  uint32_t xf_resident[2] = {kXfWaves / 4, kXfWaves / 4};  // K1, K6 workgroups resident on the device
+  uint32_t fix_resident = kXfWaves / 4;                      // k_fdct_fix workgroups resident
+  // k_fdct_fix's grid at qualities up to fix_qmax (MYYUV_FIX_GRID; 0, the
+  // default: the resident count, as above fix_qmax).  A small fixed grid
+  // measured no faster (profiles/r4h_fix_ab.txt), and busy content at low q
+  // can list far more units than the bench frame's 0.07 %.
+  uint32_t fix_grid = 0;
+  uint32_t fix_qmax = 75;  // (MYYUV_FIX_QMAX)
+  uint32_t launch_blocks = kMaxLaunchBlocks;  // blocks per launch (MYYUV_LAUNCH_BLOCKS: a test of the batch split)
+  // encoder: K1 -> K2 through HBM (split), or the fused single-pass kernel
+  // k_encode_tile (MYYUV_ENCODER=fused|split)
+  bool fused = false;
+  // decoder: the fused k_decode_idct (default), or K5 -> K6 through HBM
+  // (MYYUV_DECODER=split)
+  bool fused_dec = true;
+  // chained scan (k_chain.hpp): per-tile status words tagged with the launch
+  // epoch, counted here
+  DevBuf status;
+  uint32_t epoch = 0;
+  // quantisation tables of the last quality triple (host copy; qtd on the
+  // device, rewritten in stream order when the triple changes)
+  QTables qt;
+  hipStream_t qt_stream = nullptr;
+  uint8_t q_cached[3] = {0, 0, 0};
+  bool q_valid = false;
+  // profiling: the kernels' start/stop events until drain_profile reads
+  // them; they are used again from launch to launch
+  struct Stamp {
+    int kid;
+    Event start, stop;
+  };
+  uint32_t prof = 0;  // bit k: stamp kernel id k
+  uint32_t skip = 0;  // diagnostic: bit k: do not launch kernel id k (myyuv_debug_skip_kernels)
+  double ms[MYYUV_K_COUNT] = {};
+  int64_t launches[MYYUV_K_COUNT] = {};
+  std::vector<Stamp> pending;
+  std::vector<Event> free_events;
+  // set once every piece of it exists (pipe_init)
+  std::unique_ptr<HostPipe> pipe;
+  std::mutex mu;
+  // Waits for everything the context queued (under a DeviceGuard of its device).
+  ~myyuv_hip_ctx();
+};
+
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) (void)hipSetDevice(dev);
+  }
+  ~DeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+
+// Orders a call on stream `s` after the context's previous call (see
+// myyuv_hip_ctx::done); the record at scope exit publishes this call's work.
+struct StreamOrder {
+  myyuv_hip_ctx* c;
+  hipStream_t s;
+  StreamOrder(myyuv_hip_ctx* ctx, hipStream_t st) : c(ctx), s(st) {
+    if (c->last_stream && c->last_stream != s) (void)hipStreamWaitEvent(s, c->done, 0);
+  }
+  ~StreamOrder() {
+    if (hipEventRecord(c->done, s) == hipSuccess) c->last_stream = s;
+  }
+};
+
+// An entry point's prologue: the context's lock, its device, the call's
+// stream (NULL: the context's own) and its place in the call order.
+struct Entry {
+  std::lock_guard<std::mutex> lock;
+  DeviceGuard dev;
+  hipStream_t s;
+  StreamOrder order;
+  explicit Entry(myyuv_hip_ctx* c, void* stream = nullptr)
+      : lock(c->mu), dev(c->device), s(stream ? static_cast<hipStream_t>(stream) : c->stream.h), order(c, s) {}
+};
+
+inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+
+inline Event take_event(myyuv_hip_ctx* c) {
+  Event e;
+  if (!c->free_events.empty()) {
+    e = std::move(c->free_events.back());
+    c->free_events.pop_back();
+  } else {
+    (void)hipEventCreate(&e.h);
+  }
+  return e;
+}
+
+// Launches kernel `k` on `s`.  When profiling, the start/stop events are the
+// ones hipExtLaunchKernel stamps from the kernel's own dispatch packet: the
+// kernel's execution time (what rocprofv3's kernel trace reports), without
+// the few microseconds of queue latency a hipEventRecord bracket adds.
+template <class... KArgs, class... Args>
+int launch(myyuv_hip_ctx* c, int kid, void (*k)(KArgs...), dim3 grid, dim3 block, hipStream_t s,
+           Args... args) {
+  if ((c->skip >> kid) & 1u) return 0;
+  Event a, b;
+  const bool stamp = (c->prof >> kid) & 1u;
+  if (stamp) {
+    a = take_event(c);
+    b = take_event(c);
+  }
+  hipExtLaunchKernelGGL(k, grid, block, 0, s, a.h, b.h, 0, static_cast<KArgs>(args)...);
+  if (hipPeekAtLastError() != hipSuccess) {
+    (void)hipGetLastError();
+    return MYYUV_E_HIP;
+  }
+  if (stamp) c->pending.push_back({kid, std::move(a), std::move(b)});
+  return 0;
+}
+
+// myyuv_hip.cpp
+void drain_profile(myyuv_hip_ctx* c);
+void finish_qtables(QTables& t, int planes);
+// One plane of nblocks blocks, one block wide (the block-level known-answer
+// entry points' geometry; planes 1 and 2 empty).
+FrameGeom block_geom(uint32_t nblocks);
+int reserve(myyuv_hip_ctx* c, const FrameGeom& G);
+int launch_fdct(myyuv_hip_ctx* c, const FrameGeom& G, const uint8_t* in, const QTables* qt, uint32_t* k2ctl,
+                hipStream_t s);
+int launch_huff_encode(myyuv_hip_ctx* c, const FrameGeom& G, hipStream_t s);
+
+#pragma GCC visibility pop

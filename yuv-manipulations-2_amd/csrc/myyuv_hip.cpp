@@ -6,71 +6,20 @@
 //   decompress: parse -> scan -> K5 huff_decode -> K6 dequant_idct
 // Every launch goes to one stream; nothing synchronises inside the
 // device-resident entry points, so frames pipeline back to back.
-#include <hip/hip_ext.h>
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
+// The context, the owners of its HIP resources and the entry points'
+// prologue (Entry: lock, device, stream, StreamOrder) are in host_ctx.hpp; the
+// diagnostic and known-answer entry points in myyuv_hip_diag.cpp.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <vector>
 
-#include "codec_common.hpp"
+#include "host_ctx.hpp"
+// (after the HIP runtime header)
 #include "fdct_bfly.h"
-#include "k_chain.hpp"
-#include "k_stream.hpp"
-#include "myyuv_hip.h"
 
 #ifndef MYYUV_R16_BATCH
 #define MYYUV_R16_BATCH 1  // batches take the CAP-16 overflow tier too (0: single frames only)
 #endif
-
-namespace myyuv_gpu {
-__global__ void k_fdct_quant(const uint8_t*, FrameGeom, const QTables*, uint4*, uint8_t*, uint32_t*, uint4*,
-                             uint32_t*, uint32_t*, uint32_t);
-__global__ void k_fdct_fix(const uint8_t*, FrameGeom, const QTables*, uint4*, uint8_t*, uint32_t*, uint4*,
-                           uint32_t*, uint32_t);
-__global__ void k_dequant_idct(const uint4*, const uint8_t*, const uint4*, FrameGeom, const QTables*, uint8_t*,
-                               uint4*);
-__global__ void k_decode_idct(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
-                              const uint32_t*, FrameGeom, uint32_t, uint32_t, const QTables*, uint4*, uint8_t*,
-                              unsigned long long*);
-template <uint32_t W>
-__global__ void k_huff_encode(const uint4*, const uint32_t*, const uint4*, FrameGeom, uint32_t*, uint32_t*,
-                              uint8_t*, uint32_t*, uint32_t*, uint32_t*);
-__global__ void k_huff_encode_wave(const uint4*, const uint8_t*, FrameGeom, uint32_t*, uint8_t*, uint32_t*,
-                                   const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t,
-                                   uint32_t);
-__global__ void k_huff_encode_wide(const uint4*, const uint8_t*, const uint4*, FrameGeom, uint32_t*, uint8_t*,
-                                   uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*,
-                                   uint32_t, uint32_t);
-__global__ void k_huff_encode_r16(const uint4*, const uint8_t*, const uint4*, FrameGeom, uint32_t*, uint8_t*,
-                                  uint32_t*, const uint32_t*, const uint32_t*, uint32_t*, uint32_t*, uint32_t);
-__global__ void k_encode_tile(const uint8_t*, FrameGeom, const QTables*, uint4*, uint8_t*, uint32_t*, uint32_t*,
-                              uint8_t*, uint32_t*, uint32_t*, uint32_t*);
-__global__ void k_tile_scan(uint32_t*, FrameGeom, uint8_t*, uint32_t, uint32_t*, unsigned long long*);
-__global__ void k_scan_chain(const uint8_t*, uint32_t, ScanSrc, const uint32_t*, uint32_t, FrameGeom,
-                             StreamDesc*, uint32_t*, uint32_t*, uint32_t, unsigned long long*,
-                             uint32_t, unsigned long long*);
-__global__ void k_stream_out(const uint32_t*, const uint32_t*, const uint8_t*, const uint32_t*,
-                             const uint32_t*, FrameGeom, uint8_t*, uint32_t, uint32_t);
-__global__ void k_huff_decode(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
-                              const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t,
-                              uint4*, uint8_t*, unsigned long long*);
-template <int BPP>
-__global__ void k_bmp_to_iyuv(const uint8_t*, uint32_t, uint32_t, uint32_t, uint8_t*);
-#ifdef MYYUV_STAMPS
-extern __device__ unsigned long long g_k2_stamps[40];
-extern __device__ uint32_t g_k2_wstamps[65536 * 8];
-extern __device__ uint32_t g_k2_fstamps[8192 * 8];
-extern __device__ uint32_t g_dec_wstamps[65536 * 8];
-extern __device__ uint32_t g_k2_win[65536 * 8];
-#endif
-}  // namespace myyuv_gpu
-
-using namespace myyuv_gpu;
 
 namespace {
 
@@ -90,41 +39,6 @@ void make_qtable(int q, bool chroma, float out[64]) {
   const float mul = (fq >= 50.5f) ? (100.0f - fq) / 50.0f : 50.0f / fq;
   for (int i = 0; i < 64; i++) out[i] = std::min(std::max(std::roundf(base[i] * mul), 1.0f), 255.0f);
 }
-
-// Reciprocals and K1's fast-path row bounds from the Q tables.
-void finish_qtables(QTables& t, int planes) {
-  for (int p = 0; p < planes; p++) {
-    for (int n = 0; n < 64; n++) t.r[p][n] = 1.0f / t.q[p][n];
-    myyuv_bfly::bfly_row_bounds(t.r[p], t.kb[p]);
-  }
-}
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  int grow(size_t want) {
-    if (want <= n) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    if (hipMalloc(&p, want) != hipSuccess) return MYYUV_E_HIP;
-    n = want;
-    return 0;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-constexpr uint8_t kZigzag[64] = MYYUV_ZIGZAG;
-
-uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 // K1/K6 grid: persistent waves (four per 256-thread workgroup) striding over
 // the frame's 16-block units: as many workgroups as are resident at once
@@ -172,6 +86,58 @@ int make_geom(uint32_t w, uint32_t h, FrameGeom& G) {
   return 0;
 }
 
+}  // namespace
+
+FrameGeom block_geom(uint32_t nblocks) {
+  FrameGeom G;
+  std::memset(&G, 0, sizeof(G));
+  G.pw[0] = 8;
+  G.ph[0] = 8 * nblocks;
+  G.bw[0] = 1;
+  G.bmag[0] = block_magic(1);
+  G.cum[1] = G.cum[2] = G.cum[3] = nblocks;
+  G.ucum[1] = G.ucum[2] = G.ucum[3] = ceil_div(nblocks, kXfUnit);
+  G.tcum[1] = G.tcum[2] = G.tcum[3] = ceil_div(nblocks, kK2Group);
+  G.nframes = 1;
+  G.fbytes = nblocks * 64;
+  G.umag = block_magic(G.ucum[3]);
+  return G;
+}
+
+// Reciprocals and K1's fast-path row bounds from the Q tables.
+void finish_qtables(QTables& t, int planes) {
+  for (int p = 0; p < planes; p++) {
+    for (int n = 0; n < 64; n++) t.r[p][n] = 1.0f / t.q[p][n];
+    myyuv_bfly::bfly_row_bounds(t.r[p], t.kb[p]);
+  }
+}
+
+void drain_profile(myyuv_hip_ctx* c) {
+  for (auto& it : c->pending) {
+    float ms = 0;
+    (void)hipEventSynchronize(it.stop);
+    if (hipEventElapsedTime(&ms, it.start, it.stop) == hipSuccess) {
+      c->ms[it.kid] += ms;
+      c->launches[it.kid] += 1;
+    }
+    c->free_events.push_back(std::move(it.start));
+    c->free_events.push_back(std::move(it.stop));
+  }
+  c->pending.clear();
+}
+
+myyuv_hip_ctx::~myyuv_hip_ctx() {
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (pipe) {
+    (void)hipStreamSynchronize(pipe->cin);
+    (void)hipStreamSynchronize(pipe->cout);
+  }
+  if (last_stream) (void)hipEventSynchronize(done);
+  drain_profile(this);
+}
+
+namespace {
+
 // Frames per launch of geometry G (kMaxLaunchBlocks, or a smaller
 // diagnostic cap: MYYUV_LAUNCH_BLOCKS, read at context creation).
 uint32_t launch_frames(const FrameGeom& G, uint32_t cap_blocks = kMaxLaunchBlocks) {
@@ -188,149 +154,30 @@ int set_batch(FrameGeom& G, uint32_t nf) {
   return 0;
 }
 
-}  // namespace
+// (C names, like the helpers further down that sit between the entry points:
+// the library's dynamic symbol table has always listed them, and keeps them)
+extern "C" {
 
-struct myyuv_hip_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  // One context's scratch buffers (coef, slots, sizes, scan status words ...)
-  // serve one call at a time: every entry point records `done` on its stream
-  // and a call on another stream first waits for it (StreamOrder), so calls
-  // on different streams through one context run in call order.
-  hipEvent_t done = nullptr;
-  hipStream_t last_stream = nullptr;
-  DevBuf frame, coef, sizes, loff, tiles, payload, err, psize, desc, work, qtd;
-  DevBuf stage, oslots, tinfo, srcoff;  // K2 -> K4 (codec_common.hpp)
-  DevBuf bmp;   // staged BMP pixels (host-buffer BMP -> IYUV)
-  DevBuf bsizes;  // u32 payload sizes of a host-buffer batch
-  DevBuf rmask; // per block: bit c = coefficient row c nonzero (K1 -> overflow passes, K5 -> K6)
-  DevBuf binfo; // per block: K1 -> K2's classification (binfo_word, codec_common.hpp)
-  DevBuf zq;    // 256 zero bytes: K6's source for rows the mask says are zero
-  DevBuf sink;  // K1/K6 stores of lanes past a plane's end (128 x 16 B, never read)
-  // K1 -> k_fdct_fix: the unproven units' lists and counts (fix_count /
-  // fix_list, codec_common.hpp; fix_par alternates from launch to launch)
-  DevBuf fix;
-  uint32_t fix_par = 0;
-  uint32_t xf_resident[2] = {kXfWaves / 4, kXfWaves / 4};  // K1, K6 workgroups resident on the device
-  uint32_t fix_resident = kXfWaves / 4;                      // k_fdct_fix workgroups resident
-  // k_fdct_fix's grid at qualities up to fix_qmax (MYYUV_FIX_GRID; 0, the
-  // default: the resident count, as above fix_qmax).  A small fixed grid
-  // measured no faster (profiles/r4h_fix_ab.txt), and busy content at low q
-  // can list far more units than the bench frame's 0.07 %.
-  uint32_t fix_grid = 0;
-  uint32_t fix_qmax = 75;  // (MYYUV_FIX_QMAX)
-  uint32_t launch_blocks = kMaxLaunchBlocks;  // blocks per launch (MYYUV_LAUNCH_BLOCKS: a test of the batch split)
-  // encoder: K1 -> K2 through HBM (split), or the fused single-pass kernel
-  // k_encode_tile (MYYUV_ENCODER=fused|split)
-  bool fused = false;
-  // decoder: the fused k_decode_idct (default), or K5 -> K6 through HBM
-  // (MYYUV_DECODER=split)
-  bool fused_dec = true;
-  // chained scan (k_chain.hpp): per-tile status words tagged with the launch
-  // epoch, counted here
-  DevBuf status;
-  uint32_t epoch = 0;
-  // quantisation tables of the last quality triple (host copy; qtd on the
-  // device, rewritten in stream order when the triple changes)
-  QTables qt;
-  hipStream_t qt_stream = nullptr;
-  uint8_t q_cached[3] = {0, 0, 0};
-  bool q_valid = false;
-  // profiling
-  uint32_t prof = 0;  // bit k: stamp kernel id k
-  uint32_t skip = 0;  // diagnostic: bit k: do not launch kernel id k (myyuv_debug_skip_kernels)
-  double ms[MYYUV_K_COUNT] = {};
-  int64_t launches[MYYUV_K_COUNT] = {};
-  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
-  std::vector<hipEvent_t> free_events;
-  // host-buffer batch pipeline (HostPipe below): H2D on cin, kernels on
-  // `stream`, D2H on cout; two slots of up to kPipeMaxChunk frames
-  hipStream_t cin = nullptr, cout = nullptr;
-  hipEvent_t pev[3][2] = {};  // [copied in, computed, copied out][slot]
-  DevBuf pin[2], pout[2], psz[2], perr[2];
-  uint32_t* hsz = nullptr;            // pinned: 2 x kPipeMaxChunk u32 sizes
-  unsigned long long* herr = nullptr;  // pinned: 2 error words
-  std::mutex mu;
-};
-
-namespace {
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-// Orders a call on stream `s` after the context's previous call (see
-// myyuv_hip_ctx::done); the record at scope exit publishes this call's work.
-struct StreamOrder {
-  myyuv_hip_ctx* c;
-  hipStream_t s;
-  StreamOrder(myyuv_hip_ctx* ctx, hipStream_t st) : c(ctx), s(st) {
-    if (c->last_stream && c->last_stream != s) (void)hipStreamWaitEvent(s, c->done, 0);
-  }
-  ~StreamOrder() {
-    if (hipEventRecord(c->done, s) == hipSuccess) c->last_stream = s;
-  }
-};
-
-hipEvent_t take_event(myyuv_hip_ctx* c) {
-  if (!c->free_events.empty()) {
-    hipEvent_t e = c->free_events.back();
-    c->free_events.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
-}
-
-// Launches kernel `k` on `s`.  When profiling, the start/stop events are the
-// ones hipExtLaunchKernel stamps from the kernel's own dispatch packet: the
-// kernel's execution time (what rocprofv3's kernel trace reports), without
-// the few microseconds of queue latency a hipEventRecord bracket adds.
-template <class... KArgs, class... Args>
-int launch(myyuv_hip_ctx* c, int kid, void (*k)(KArgs...), dim3 grid, dim3 block, hipStream_t s,
-           Args... args) {
-  if ((c->skip >> kid) & 1u) return 0;
-  hipEvent_t a = nullptr, b = nullptr;
-  const bool stamp = (c->prof >> kid) & 1u;
-  if (stamp) {
-    a = take_event(c);
-    b = take_event(c);
-  }
-  hipExtLaunchKernelGGL(k, grid, block, 0, s, a, b, 0, static_cast<KArgs>(args)...);
-  if (hipPeekAtLastError() != hipSuccess) {
-    (void)hipGetLastError();
-    return MYYUV_E_HIP;
-  }
-  if (stamp) c->pending.push_back({kid, {a, b}});
+int check_q(const uint8_t q[3]) {
+  for (int p = 0; p < 3; p++)
+    if (q[p] < 1 || q[p] > 100) return MYYUV_E_QUALITY;
   return 0;
 }
 
-void drain_profile(myyuv_hip_ctx* c) {
-  for (auto& it : c->pending) {
-    float ms = 0;
-    (void)hipEventSynchronize(it.second.second);
-    if (hipEventElapsedTime(&ms, it.second.first, it.second.second) == hipSuccess) {
-      c->ms[it.first] += ms;
-      c->launches[it.first] += 1;
-    }
-    c->free_events.push_back(it.second.first);
-    c->free_events.push_back(it.second.second);
-  }
-  c->pending.clear();
+// The kernels' error word (record_error, k_stream.hip) -> code, with the
+// failing block counted from the call's first frame: the launch began at
+// frame f0, nblk blocks per frame.  ~0: no error; a key of 0: no block.
+int chunk_err(unsigned long long v, uint32_t f0, uint32_t nblk, int64_t* bad_block) {
+  if (v == ~0ull) return 0;
+  const uint64_t key = v >> 8;
+  if (bad_block) *bad_block = key == 0 ? -1 : (int64_t)(key >> 1) + (int64_t)f0 * nblk;
+  return (int)(v & 0xFF);
 }
 
+}  // extern "C"
+
 int set_qtables(myyuv_hip_ctx* c, const uint8_t q[3], hipStream_t s) {
-  for (int p = 0; p < 3; p++)
-    if (q[p] < 1 || q[p] > 100) return MYYUV_E_QUALITY;
+  if (int e = check_q(q)) return e;
   if (c->q_valid && std::memcmp(c->q_cached, q, 3) == 0 && c->qt_stream == s) return 0;
   for (int p = 0; p < 3; p++) {
     make_qtable(q[p], p != 0, c->qt.q[p]);
@@ -348,6 +195,8 @@ int set_qtables(myyuv_hip_ctx* c, const uint8_t q[3], hipStream_t s) {
   c->q_valid = true;
   return 0;
 }
+
+}  // namespace
 
 // Workspace for a batch of G.nframes frames (blocks numbered batch-globally;
 // scan tiles, stream descriptors and look-back status words per frame).
@@ -397,6 +246,8 @@ int reserve(myyuv_hip_ctx* c, const FrameGeom& G) {
   return e ? MYYUV_E_HIP : 0;
 }
 
+namespace {
+
 uint32_t next_epoch(myyuv_hip_ctx* c) {
   c->epoch = (c->epoch + 1) & kEpochMask;
   if (c->epoch == 0) c->epoch = 1;  // status words start zeroed: epoch 0 is never current
@@ -415,23 +266,6 @@ uint32_t next_epoch(myyuv_hip_ctx* c) {
 // through the CAP-16 register tier first (k_huff_encode_r16), and the two
 // passes then take what it leaves (more than 16 symbols: work[1] blocks from
 // word 64 + nblk).  work[0] is zeroed by K1 (or the host), work[1] here.
-int launch_overflow(myyuv_hip_ctx* c, const FrameGeom& G, hipStream_t s);
-
-int launch_huff_encode(myyuv_hip_ctx* c, const FrameGeom& G, hipStream_t s) {
-  const uint32_t nf = G.nframes;
-  uint32_t* count = c->work.as<uint32_t>();
-  uint32_t* list = count + 64;
-  // (*count was zeroed by K1, just before in the stream: k_fdct_quant's k2ctl)
-  // (the window size of the launch, k2_win: K4 uses the same)
-  const uint32_t W = k2_win(nf * G.tcum[3]);
-  const int e = launch(c, MYYUV_K_HUFF_ENC, W == kWinTilesBig ? k_huff_encode<kWinTilesBig> : k_huff_encode<kWinTiles>,
-                       dim3(ceil_div(nf * G.tcum[3], W)), dim3(kK2Group), s,
-               c->coef.as<const uint4>(), c->binfo.as<const uint32_t>(), c->zq.as<const uint4>(), G,
-               c->stage.as<uint32_t>(), c->tinfo.as<uint32_t>(), c->sizes.as<uint8_t>(),
-               c->srcoff.as<uint32_t>(), list, count);
-  return e | launch_overflow(c, G, s);
-}
-
 int launch_overflow(myyuv_hip_ctx* c, const FrameGeom& G, hipStream_t s) {
   const uint32_t nf = G.nframes, nblk = G.cum[3] * nf;
   uint32_t* count = c->work.as<uint32_t>();
@@ -468,6 +302,23 @@ int launch_overflow(myyuv_hip_ctx* c, const FrameGeom& G, hipStream_t s) {
   return e;
 }
 
+}  // namespace
+
+int launch_huff_encode(myyuv_hip_ctx* c, const FrameGeom& G, hipStream_t s) {
+  const uint32_t nf = G.nframes;
+  uint32_t* count = c->work.as<uint32_t>();
+  uint32_t* list = count + 64;
+  // (*count was zeroed by K1, just before in the stream: k_fdct_quant's k2ctl)
+  // (the window size of the launch, k2_win: K4 uses the same)
+  const uint32_t W = k2_win(nf * G.tcum[3]);
+  const int e = launch(c, MYYUV_K_HUFF_ENC, W == kWinTilesBig ? k_huff_encode<kWinTilesBig> : k_huff_encode<kWinTiles>,
+                       dim3(ceil_div(nf * G.tcum[3], W)), dim3(kK2Group), s,
+               c->coef.as<const uint4>(), c->binfo.as<const uint32_t>(), c->zq.as<const uint4>(), G,
+               c->stage.as<uint32_t>(), c->tinfo.as<uint32_t>(), c->sizes.as<uint8_t>(),
+               c->srcoff.as<uint32_t>(), list, count);
+  return e | launch_overflow(c, G, s);
+}
+
 // K1, then its exact path for the units it listed (k_fdct_fix).  The list
 // is on the device, so the fix grid cannot follow its length: the resident
 // count (the fast path fails for 0.07 % of the bench frame's units at q50,
@@ -498,6 +349,8 @@ int launch_fdct(myyuv_hip_ctx* c, const FrameGeom& G, const uint8_t* in, const Q
     e |= hipMemsetAsync(fix_count(c->fix.as<uint32_t>(), par ^ 1u, 0), 0, kFixLists * 32 * 4, s) != hipSuccess;
   return e;
 }
+
+namespace {
 
 // One batch of G.nframes frames (frame f at d_in + f * fbytes), payload f at
 // d_out + f * cap, its size at d_size[f].
@@ -576,12 +429,12 @@ int launch_decompress(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_in,
 // pcie_copy.cpp, profiles/r3b_pcie_copy.txt: 18 MB in 0.33-0.43 ms, a fresh
 // or 1-byte-misaligned buffer included), faster than staging through pinned
 // chunks with a CPU copy (0.47-0.59 ms H2D, 1.1-2.7 ms D2H).
-int h2d(myyuv_hip_ctx*, void* dst, const void* src, size_t n, hipStream_t s) {
+int h2d(void* dst, const void* src, size_t n, hipStream_t s) {
   return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s) == hipSuccess ? 0 : MYYUV_E_HIP;
 }
 
 // (synchronous: returns when dst holds the bytes)
-int d2h(myyuv_hip_ctx*, void* dst, const void* src, size_t n, hipStream_t s) {
+int d2h(void* dst, const void* src, size_t n, hipStream_t s) {
   return hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess
              ? 0
              : MYYUV_E_HIP;
@@ -596,11 +449,7 @@ int read_err(myyuv_hip_ctx* c, hipStream_t s, int64_t* bad_block) {
   if (hipMemcpyAsync(&v, c->err.p, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return MYYUV_E_HIP;
   if (hipStreamSynchronize(s) != hipSuccess) return MYYUV_E_HIP;
   if (bad_block) *bad_block = -1;
-  if (v == ~0ull) return 0;
-  const int code = (int)(v & 0xFF);
-  const uint64_t key = v >> 8;
-  if (bad_block) *bad_block = key == 0 ? -1 : (int64_t)(key >> 1);
-  return code;
+  return chunk_err(v, 0, 0, bad_block);
 }
 
 // Host mirror of the stream header checks (parse_stream, k_chain.hpp; same order), for host buffers.
@@ -632,6 +481,35 @@ bool hip_ok() {
     ok = (hipGetDeviceCount(&n) == hipSuccess && n > 0) ? 1 : 0;
   }
   return ok == 1;
+}
+
+// The device-resident codec calls, both directions (compress: frames ->
+// payloads; frame f at d_frames + f * fbytes, payload f at d_payloads +
+// f * cap, its size at d_sizes[f]).  Nothing synchronises.
+int batch_device(bool compress, myyuv_hip_ctx* c, void* d_frames, void* d_payloads, uint32_t* d_sizes,
+                 uint32_t cap, uint32_t nframes, uint32_t w, uint32_t h, const uint8_t q[3], void* stream) {
+  if (!c || !d_frames || !d_payloads || !d_sizes || !q) return MYYUV_E_ARG;
+  if (((uintptr_t)d_payloads & 3) || ((uintptr_t)d_frames & 7) || (nframes > 1 && (cap & 3)))
+    return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = check_q(q);
+  if (e || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes))) return e;
+  Entry en(c, stream);
+  // (as several launches when the batch's coefficient image would reach 4 GiB)
+  const uint32_t per = launch_frames(G, c->launch_blocks);
+  FrameGeom GL = G;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve(c, GL)) || (e = set_qtables(c, q, en.s))) return e;
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GL.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
+    uint8_t* fr = static_cast<uint8_t*>(d_frames) + (size_t)f0 * G.fbytes;
+    uint8_t* pay = static_cast<uint8_t*>(d_payloads) + (size_t)f0 * cap;
+    if ((e = compress ? launch_compress(c, GL, fr, pay, cap, d_sizes + f0, en.s)
+                      : launch_decompress(c, GL, pay, d_sizes + f0, cap, fr, en.s)))
+      return e;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -674,18 +552,12 @@ int myyuv_hip_create(int device, myyuv_hip_handle* out) {
   if (!hip_ok()) return MYYUV_E_NO_DEVICE;
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return MYYUV_E_NO_DEVICE;
-  DeviceGuard g(device);
-  auto* c = new myyuv_hip_ctx();
+  DeviceGuard g(device);  // (declared before c: it outlives the context on a failure)
+  auto c = std::make_unique<myyuv_hip_ctx>();
   c->device = device;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete c;
+  if (hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&c->done.h, hipEventDisableTiming) != hipSuccess)
     return MYYUV_E_HIP;
-  }
-  if (hipEventCreateWithFlags(&c->done, hipEventDisableTiming) != hipSuccess) {
-    (void)hipStreamDestroy(c->stream);
-    delete c;
-    return MYYUV_E_HIP;
-  }
   {
     int cus = 0, n1 = 0, n6 = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
@@ -718,111 +590,31 @@ int myyuv_hip_create(int device, myyuv_hip_handle* out) {
     }
   }
   if (c->err.grow(8) || c->psize.grow(4) || c->desc.grow(sizeof(StreamDesc)) ||
-      hipMemset(c->err.p, 0xFF, 8) != hipSuccess) {
-    (void)hipEventDestroy(c->done);
-    (void)hipStreamDestroy(c->stream);
-    delete c;
+      hipMemset(c->err.p, 0xFF, 8) != hipSuccess)
     return MYYUV_E_HIP;
-  }
-  *out = c;
+  *out = c.release();
   return 0;
 }
 
 void myyuv_hip_destroy(myyuv_hip_handle c) {
   if (!c) return;
   DeviceGuard g(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  if (c->last_stream) (void)hipEventSynchronize(c->done);
-  drain_profile(c);
-  for (auto e : c->free_events) (void)hipEventDestroy(e);
-  (void)hipEventDestroy(c->done);
-  DevBuf* bufs[] = {&c->frame, &c->coef, &c->stage, &c->oslots, &c->tinfo, &c->srcoff, &c->sizes, &c->loff, &c->tiles, &c->payload,
-                    &c->err,   &c->qtd,  &c->psize, &c->desc,  &c->work,  &c->status, &c->sink,
-                    &c->bmp,   &c->rmask, &c->zq, &c->bsizes, &c->fix, &c->binfo,
-                    &c->pin[0], &c->pin[1], &c->pout[0], &c->pout[1], &c->psz[0], &c->psz[1],
-                    &c->perr[0], &c->perr[1]};
-  for (auto* b : bufs) b->release();
-  if (c->cin) {
-    (void)hipStreamSynchronize(c->cin);
-    (void)hipStreamSynchronize(c->cout);
-    (void)hipStreamDestroy(c->cin);
-    (void)hipStreamDestroy(c->cout);
-    for (auto& row : c->pev)
-      for (auto e : row) (void)hipEventDestroy(e);
-    (void)hipHostFree(c->hsz);
-    (void)hipHostFree(c->herr);
-  }
-  (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
-int myyuv_hip_reserve(myyuv_hip_handle c, uint32_t w, uint32_t h) {
-  if (!c) return MYYUV_E_ARG;
-  FrameGeom G;
-  int e = make_geom(w, h, G);
-  if (e) return e;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  return reserve(c, G);
-}
+int myyuv_hip_reserve(myyuv_hip_handle c, uint32_t w, uint32_t h) { return myyuv_hip_reserve_batch(c, w, h, 1); }
 
 int myyuv_gpu_dct_compress_batch_device(myyuv_hip_handle c, const void* d_in, uint32_t nframes,
                                         uint32_t w, uint32_t h, const uint8_t q[3], void* d_out,
                                         uint32_t cap, uint32_t* d_sizes, void* stream) {
-  if (!c || !d_in || !d_out || !d_sizes || !q) return MYYUV_E_ARG;
-  if (((uintptr_t)d_out & 3) || ((uintptr_t)d_in & 7) || (nframes > 1 && (cap & 3)))
-    return MYYUV_E_ARG;
-  for (int p = 0; p < 3; p++)
-    if (q[p] < 1 || q[p] > 100) return MYYUV_E_QUALITY;
-  FrameGeom G;
-  int e = make_geom(w, h, G);
-  if (e || (e = set_batch(G, nframes))) return e;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-  StreamOrder so(c, s);
-  // (as several launches when the batch's coefficient image would reach 4 GiB)
-  const uint32_t per = launch_frames(G, c->launch_blocks);
-  FrameGeom GL = G;
-  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve(c, GL)) || (e = set_qtables(c, q, s))) return e;
-  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
-    GL = G;
-    GL.fbase = f0;
-    if ((e = set_batch(GL, std::min(per, nframes - f0))) ||
-        (e = launch_compress(c, GL, static_cast<const uint8_t*>(d_in) + (size_t)f0 * G.fbytes,
-                             static_cast<uint8_t*>(d_out) + (size_t)f0 * cap, cap, d_sizes + f0, s)))
-      return e;
-  }
-  return 0;
+  return batch_device(true, c, const_cast<void*>(d_in), d_out, d_sizes, cap, nframes, w, h, q, stream);
 }
 
 int myyuv_gpu_dct_decompress_batch_device(myyuv_hip_handle c, const void* d_in, const uint32_t* d_sizes,
                                           uint32_t cap, uint32_t nframes, uint32_t w, uint32_t h,
                                           const uint8_t q[3], void* d_out, void* stream) {
-  if (!c || !d_in || !d_out || !d_sizes || !q) return MYYUV_E_ARG;
-  if (((uintptr_t)d_in & 3) || ((uintptr_t)d_out & 7) || (nframes > 1 && (cap & 3)))
-    return MYYUV_E_ARG;
-  for (int p = 0; p < 3; p++)
-    if (q[p] < 1 || q[p] > 100) return MYYUV_E_QUALITY;
-  FrameGeom G;
-  int e = make_geom(w, h, G);
-  if (e || (e = set_batch(G, nframes))) return e;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-  StreamOrder so(c, s);
-  const uint32_t per = launch_frames(G, c->launch_blocks);
-  FrameGeom GL = G;
-  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve(c, GL)) || (e = set_qtables(c, q, s))) return e;
-  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
-    GL = G;
-    GL.fbase = f0;
-    if ((e = set_batch(GL, std::min(per, nframes - f0))) ||
-        (e = launch_decompress(c, GL, static_cast<const uint8_t*>(d_in) + (size_t)f0 * cap, d_sizes + f0, cap,
-                               static_cast<uint8_t*>(d_out) + (size_t)f0 * G.fbytes, s)))
-      return e;
-  }
-  return 0;
+  return batch_device(false, c, d_out, const_cast<void*>(d_in), const_cast<uint32_t*>(d_sizes), cap, nframes, w, h,
+                      q, stream);
 }
 
 int myyuv_gpu_dct_compress_device(myyuv_hip_handle c, const void* d_in, uint32_t w, uint32_t h,
@@ -894,10 +686,8 @@ int myyuv_gpu_bmp_to_iyuv_device(myyuv_hip_handle c, const void* d_bmp, int32_t 
   uint32_t W = 0, H = 0, orient = 0;
   int e = bmp_check(width, height, bit_count, &W, &H, &orient);
   if (e) return e;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-  StreamOrder so(c, s);
+  Entry en(c, stream);
+  hipStream_t s = en.s;
   return launch_bmp(c, d_bmp, W, H, orient, bit_count, d_iyuv, s);
 }
 
@@ -907,26 +697,22 @@ int myyuv_gpu_bmp_to_iyuv(myyuv_hip_handle c, const uint8_t* bmp_data, int32_t w
   uint32_t W = 0, H = 0, orient = 0;
   int e = bmp_check(width, height, bit_count, &W, &H, &orient);
   if (e) return e;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  hipStream_t s = c->stream;
-  StreamOrder so(c, s);
+  Entry en(c);
+  hipStream_t s = en.s;
   const size_t in_bytes = (size_t)W * H * (bit_count / 8), out_bytes = (size_t)W * H * 3 / 2;
   if (in_bytes == 0) return 0;
   if (c->bmp.grow(in_bytes) || c->frame.grow(out_bytes)) return MYYUV_E_HIP;
-  if (h2d(c, c->bmp.p, bmp_data, in_bytes, s)) return MYYUV_E_HIP;
+  if (h2d(c->bmp.p, bmp_data, in_bytes, s)) return MYYUV_E_HIP;
   if ((e = launch_bmp(c, c->bmp.p, W, H, orient, bit_count, c->frame.p, s))) return e;
-  if (d2h(c, iyuv, c->frame.p, out_bytes, s)) return MYYUV_E_HIP;
+  if (d2h(iyuv, c->frame.p, out_bytes, s)) return MYYUV_E_HIP;
   if (c->prof) drain_profile(c);
   return 0;
 }
 
 int myyuv_hip_sync_status(myyuv_hip_handle c, void* stream, int64_t* bad_block) {
   if (!c) return MYYUV_E_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-  StreamOrder so(c, s);
+  Entry en(c, stream);
+  hipStream_t s = en.s;
   int code = read_err(c, s, bad_block);
   if (reset_err(c, s) || hipStreamSynchronize(s) != hipSuccess) return MYYUV_E_HIP;
   if (c->prof) drain_profile(c);
@@ -937,21 +723,17 @@ int myyuv_gpu_dct_compress(myyuv_hip_handle c, const uint8_t* iyuv, uint32_t w, 
                            const uint8_t q[3], uint8_t* payload, uint32_t cap,
                            uint32_t* payload_size) {
   if (!c || !iyuv || !payload || !payload_size || !q) return MYYUV_E_ARG;
-  for (int p = 0; p < 3; p++)
-    if (q[p] < 1 || q[p] > 100) return MYYUV_E_QUALITY;
   FrameGeom G;
-  int e = make_geom(w, h, G);
-  if (e) return e;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  hipStream_t s = c->stream;
-  StreamOrder so(c, s);
+  int e = check_q(q);
+  if (e || (e = make_geom(w, h, G))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
   const size_t fbytes = (size_t)w * h * 3 / 2;
   const uint32_t bound = myyuv_dct_payload_bound(w, h);
   if ((e = reserve(c, G)) || (e = set_qtables(c, q, s))) return e;
   if (c->frame.grow(fbytes) || c->payload.grow(bound)) return MYYUV_E_HIP;
   if (reset_err(c, s)) return MYYUV_E_HIP;
-  if (h2d(c, c->frame.p, iyuv, fbytes, s)) return MYYUV_E_HIP;
+  if (h2d(c->frame.p, iyuv, fbytes, s)) return MYYUV_E_HIP;
   if ((e = launch_compress(c, G, c->frame.p, c->payload.p, bound, c->psize.as<uint32_t>(), s)))
     return e;
   uint32_t size = 0;
@@ -965,7 +747,7 @@ int myyuv_gpu_dct_compress(myyuv_hip_handle c, const uint8_t* iyuv, uint32_t w, 
   }
   *payload_size = size;
   if (size > cap) return MYYUV_E_CAPACITY;
-  if (d2h(c, payload, c->payload.p, size, s)) return MYYUV_E_HIP;
+  if (d2h(payload, c->payload.p, size, s)) return MYYUV_E_HIP;
   if (c->prof) drain_profile(c);
   return 0;
 }
@@ -974,27 +756,22 @@ int myyuv_gpu_dct_decompress(myyuv_hip_handle c, const uint8_t* payload, uint32_
                              uint32_t h, const uint8_t q[3], uint8_t* iyuv, int64_t* bad_block) {
   if (bad_block) *bad_block = -1;
   if (!c || !payload || !iyuv || !q) return MYYUV_E_ARG;
-  int e_hdr = 0;
-  for (int p = 0; p < 3; p++)
-    if (q[p] < 1 || q[p] > 100) return MYYUV_E_QUALITY;
+  int e = check_q(q);
+  if (e) return e;
   // DCTYUV::load / DCTYUVPlane::load checks (DCT.cpp:454 -> :130-159, :39-62)
   // come before the dimension checks in the reference: validate the stream
   // header on the host (the device re-checks it in k_scan_chain).
-  if ((e_hdr = host_parse_headers(payload, size))) return e_hdr;
   FrameGeom G;
-  int e = make_geom(w, h, G);
-  if (e) return e;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  hipStream_t s = c->stream;
-  StreamOrder so(c, s);
+  if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
   const uint32_t cap = (size + 3) & ~3u;
   const size_t fbytes = (size_t)w * h * 3 / 2;
   if ((e = reserve(c, G)) || (e = set_qtables(c, q, s))) return e;
   if (c->frame.grow(fbytes) || c->payload.grow(cap)) return MYYUV_E_HIP;
   if (reset_err(c, s)) return MYYUV_E_HIP;
   if (hipMemsetAsync(static_cast<uint8_t*>(c->payload.p) + (cap - 4), 0, 4, s) != hipSuccess ||
-      h2d(c, c->payload.p, payload, size, s) ||
+      h2d(c->payload.p, payload, size, s) ||
       hipMemcpyAsync(c->psize.p, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
     return MYYUV_E_HIP;
   if ((e = launch_decompress(c, G, c->payload.p, c->psize.as<const uint32_t>(), cap, c->frame.p, s)))
@@ -1004,7 +781,7 @@ int myyuv_gpu_dct_decompress(myyuv_hip_handle c, const uint8_t* payload, uint32_
     (void)hipStreamSynchronize(s);
     return e;
   }
-  if (d2h(c, iyuv, c->frame.p, fbytes, s)) return MYYUV_E_HIP;
+  if (d2h(iyuv, c->frame.p, fbytes, s)) return MYYUV_E_HIP;
   if (c->prof) drain_profile(c);
   return 0;
 }
@@ -1020,20 +797,13 @@ int myyuv_gpu_dct_decompress(myyuv_hip_handle c, const uint8_t* payload, uint32_
 // goes straight between the caller's (pageable) buffers and the slot.
 namespace {
 
-constexpr uint32_t kPipeMaxChunk = 8;
 // MYYUV_PIPE_TRACE=1: one stderr line per pipeline step (diagnostic)
 bool pipe_trace() {
   static int t = -1;
   if (t < 0) t = std::getenv("MYYUV_PIPE_TRACE") ? 1 : 0;
   return t == 1;
 }
-#define PIPE_TRACE(...)                   \
-  do {                                    \
-    if (pipe_trace()) {                   \
-      std::fprintf(stderr, __VA_ARGS__);  \
-      std::fflush(stderr);                \
-    }                                     \
-  } while (0)
+#define PIPE_TRACE(...) (pipe_trace() ? (void)(std::fprintf(stderr, __VA_ARGS__), std::fflush(stderr)) : (void)0)
 constexpr size_t kPipeSlotBytes = (size_t)2 << 30;  // per slot: chunk frames x (input + output) bytes
 
 // frames per chunk: about 8 chunks per batch (the first chunk's upload and
@@ -1045,25 +815,28 @@ uint32_t pipe_chunk(uint32_t nf, size_t per_frame) {
   return b;
 }
 
+// Builds the pipeline on first use.  The context gets it only when every
+// piece exists: a failure leaves the context as it was, and the next call
+// tries again.
 int pipe_init(myyuv_hip_ctx* c) {
-  if (c->cin) return 0;
-  if (hipStreamCreateWithFlags(&c->cin, hipStreamNonBlocking) != hipSuccess) return MYYUV_E_HIP;
-  if (hipStreamCreateWithFlags(&c->cout, hipStreamNonBlocking) != hipSuccess) {
-    (void)hipStreamDestroy(c->cin);
-    c->cin = nullptr;
+  if (c->pipe) return 0;
+  auto p = std::make_unique<HostPipe>();
+  if (hipStreamCreateWithFlags(&p->cin.h, hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithFlags(&p->cout.h, hipStreamNonBlocking) != hipSuccess)
     return MYYUV_E_HIP;
-  }
   int e = 0;
-  for (auto& row : c->pev)
-    for (auto& ev : row) e |= hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess;
-  e |= hipHostMalloc((void**)&c->hsz, 2 * kPipeMaxChunk * 4, hipHostMallocDefault) != hipSuccess;
-  e |= hipHostMalloc((void**)&c->herr, 2 * 8, hipHostMallocDefault) != hipSuccess;
+  for (auto& row : p->pev)
+    for (auto& ev : row) e |= hipEventCreateWithFlags(&ev.h, hipEventDisableTiming) != hipSuccess;
+  e |= hipHostMalloc(&p->hsz.h, 2 * kPipeMaxChunk * 4, hipHostMallocDefault) != hipSuccess;
+  e |= hipHostMalloc(&p->herr.h, 2 * 8, hipHostMallocDefault) != hipSuccess;
   for (int k = 0; k < 2; k++) {
-    e |= c->psz[k].grow(kPipeMaxChunk * 4);
-    e |= c->perr[k].grow(8);
-    if (!e) e |= hipMemset(c->perr[k].p, 0xFF, 8) != hipSuccess;
+    e |= p->psz[k].grow(kPipeMaxChunk * 4);
+    e |= p->perr[k].grow(8);
+    if (!e) e |= hipMemset(p->perr[k].p, 0xFF, 8) != hipSuccess;
   }
-  return e ? MYYUV_E_HIP : 0;
+  if (e) return MYYUV_E_HIP;
+  c->pipe = std::move(p);
+  return 0;
 }
 
 // Waits for every pipeline stream (an early return must not leave copies to
@@ -1071,152 +844,137 @@ int pipe_init(myyuv_hip_ctx* c) {
 struct PipeDrain {
   myyuv_hip_ctx* c;
   ~PipeDrain() {
-    (void)hipStreamSynchronize(c->cin);
+    (void)hipStreamSynchronize(c->pipe->cin);
     (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->cout);
+    (void)hipStreamSynchronize(c->pipe->cout);
   }
 };
 
-// A chunk's error word (read_err's encoding) -> code, with the failing block
-// made batch-global (chunk's first frame f0, nblk blocks per frame).
-int chunk_err(unsigned long long v, uint32_t f0, uint32_t nblk, int64_t* bad_block) {
-  if (v == ~0ull) return 0;
-  const uint64_t key = v >> 8;
-  if (bad_block) *bad_block = key == 0 ? -1 : (int64_t)(key >> 1) + (int64_t)f0 * nblk;
-  return (int)(v & 0xFF);
+// The pipeline of both directions (tag: 'c' / 'd' in the trace).  A frame
+// takes in_slot / out_slot bytes of a slot's input / output buffer.  The
+// direction's own steps, each for the n frames from f0 on in slot sl:
+//   upload(P, sl, f0, n)       queues the chunk's host -> device copies on P.cin
+//   run(P, GK, sl, perr, s)    launches its kernels on s (error word: perr)
+//   download(P, sl, f0, n)     once they are done: queues the device -> host copies on P.cout
+extern "C++" template <class Upload, class Run, class Download>
+int pipe_frames(myyuv_hip_ctx* c, char tag, uint32_t nf, uint32_t w, uint32_t h, const uint8_t q[3],
+                size_t in_slot, size_t out_slot, int64_t* bad_block, Upload upload, Run run, Download download) {
+  FrameGeom G;
+  int e = make_geom(w, h, G);
+  if (e) return e;
+  const uint32_t B = std::min(pipe_chunk(nf, in_slot + out_slot), launch_frames(G, c->launch_blocks));
+  FrameGeom GB = G;
+  if ((e = set_batch(GB, B))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  if ((e = pipe_init(c)) || (e = reserve(c, GB)) || (e = set_qtables(c, q, s))) return e;
+  HostPipe& P = *c->pipe;
+  for (int k = 0; k < 2; k++)
+    if (P.pin[k].grow(in_slot * B) || P.pout[k].grow(out_slot * B)) return MYYUV_E_HIP;
+  PipeDrain drain{c};
+  const uint32_t nchunks = ceil_div(nf, B);
+  // chunk k's sizes and error word are on the host: its results go back
+  auto finish = [&](uint32_t k) -> int {
+    const uint32_t sl = k & 1, f0 = k * B, n = std::min(B, nf - f0);
+    PIPE_TRACE("pipe %c finish %u: wait kernels\n", tag, k);
+    if (hipEventSynchronize(P.pev[1][sl]) != hipSuccess) return MYYUV_E_HIP;
+    PIPE_TRACE("pipe %c finish %u: kernels done\n", tag, k);
+    if (int ce = chunk_err(*P.err(sl), f0, G.cum[3], bad_block)) return ce;
+    if (int de = download(P, sl, f0, n)) return de;
+    PIPE_TRACE("pipe %c finish %u: downloads queued\n", tag, k);
+    return hipEventRecord(P.pev[2][sl], P.cout) == hipSuccess ? 0 : MYYUV_E_HIP;
+  };
+  PIPE_TRACE("pipe %c: %u frames, chunks of %u\n", tag, nf, B);
+  for (uint32_t k = 0; k < nchunks; k++) {
+    const uint32_t sl = k & 1, f0 = k * B, n = std::min(B, nf - f0);
+    FrameGeom GK = G;
+    if ((e = set_batch(GK, n))) return e;
+    PIPE_TRACE("pipe %c chunk %u: upload\n", tag, k);
+    // upload (slot free once chunk k-2's kernels have read it)
+    if (k >= 2 && hipStreamWaitEvent(P.cin, P.pev[1][sl], 0) != hipSuccess) return MYYUV_E_HIP;
+    if ((e = upload(P, sl, f0, n))) return e;
+    if (hipEventRecord(P.pev[0][sl], P.cin) != hipSuccess) return MYYUV_E_HIP;
+    PIPE_TRACE("pipe %c chunk %u: uploads queued\n", tag, k);
+    // kernels (output slot free once chunk k-2's results are back)
+    if (hipStreamWaitEvent(s, P.pev[0][sl], 0) != hipSuccess ||
+        (k >= 2 && hipStreamWaitEvent(s, P.pev[2][sl], 0) != hipSuccess))
+      return MYYUV_E_HIP;
+    unsigned long long* perr = P.perr[sl].as<unsigned long long>();
+    if ((e = run(P, GK, sl, perr, s))) return e;
+    if (hipMemcpyAsync(P.err(sl), perr, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemsetAsync(perr, 0xFF, 8, s) != hipSuccess || hipEventRecord(P.pev[1][sl], s) != hipSuccess)
+      return MYYUV_E_HIP;
+    if (k >= 1 && (e = finish(k - 1))) return e;
+  }
+  if ((e = finish(nchunks - 1))) return e;
+  PIPE_TRACE("pipe %c: wait downloads\n", tag);
+  if (hipStreamSynchronize(P.cout) != hipSuccess) return MYYUV_E_HIP;
+  PIPE_TRACE("pipe %c: done\n", tag);
+  if (c->prof) drain_profile(c);
+  return 0;
 }
 
 int compress_frames(myyuv_hip_ctx* c, const uint8_t* const* frames, uint32_t nf, uint32_t w, uint32_t h,
                     const uint8_t q[3], myyuv_payload_alloc_fn alloc, void* user, uint32_t* sizes) {
-  FrameGeom G;
-  int e = make_geom(w, h, G);
-  if (e) return e;
   const size_t fb = (size_t)w * h * 3 / 2;
   const uint32_t dcap = (myyuv_dct_payload_bound(w, h) + 3) & ~3u;  // device slot per frame
-  const uint32_t B = std::min(pipe_chunk(nf, fb + dcap), launch_frames(G, c->launch_blocks));
-  FrameGeom GB = G;
-  if ((e = set_batch(GB, B))) return e;
-  hipStream_t s = c->stream;
-  StreamOrder so(c, s);
-  if ((e = pipe_init(c)) || (e = reserve(c, GB)) || (e = set_qtables(c, q, s))) return e;
-  for (int k = 0; k < 2; k++)
-    if (c->pin[k].grow(fb * B) || c->pout[k].grow((size_t)dcap * B)) return MYYUV_E_HIP;
-  PipeDrain drain{c};
-  const uint32_t nchunks = ceil_div(nf, B);
-  // chunk k's sizes and error word are on the host: its payloads go back
-  auto finish = [&](uint32_t k) -> int {
-    const uint32_t sl = k & 1, f0 = k * B, n = std::min(B, nf - f0);
-    PIPE_TRACE("pipe c finish %u: wait kernels\n", k);
-    if (hipEventSynchronize(c->pev[1][sl]) != hipSuccess) return MYYUV_E_HIP;
-    PIPE_TRACE("pipe c finish %u: kernels done\n", k);
-    if (int ce = chunk_err(c->herr[sl], f0, G.cum[3], nullptr)) return ce;
-    for (uint32_t i = 0; i < n; i++) {
-      const uint32_t size = c->hsz[sl * kPipeMaxChunk + i];
-      sizes[f0 + i] = size;
-      uint8_t* dst = alloc(user, f0 + i, size);
-      if (!dst) return MYYUV_E_CAPACITY;
-      if (hipMemcpyAsync(dst, c->pout[sl].as<uint8_t>() + (size_t)i * dcap, size, hipMemcpyDeviceToHost,
-                         c->cout) != hipSuccess)
-        return MYYUV_E_HIP;
-    }
-    PIPE_TRACE("pipe c finish %u: downloads queued\n", k);
-    return hipEventRecord(c->pev[2][sl], c->cout) == hipSuccess ? 0 : MYYUV_E_HIP;
-  };
-  PIPE_TRACE("pipe c: %u frames, chunks of %u\n", nf, B);
-  for (uint32_t k = 0; k < nchunks; k++) {
-    const uint32_t sl = k & 1, f0 = k * B, n = std::min(B, nf - f0);
-    FrameGeom GK = G;
-    if ((e = set_batch(GK, n))) return e;
-    PIPE_TRACE("pipe c chunk %u: upload\n", k);
-    // upload (slot free once chunk k-2's kernels have read it)
-    if (k >= 2 && hipStreamWaitEvent(c->cin, c->pev[1][sl], 0) != hipSuccess) return MYYUV_E_HIP;
-    for (uint32_t i = 0; i < n; i++)
-      if (hipMemcpyAsync(c->pin[sl].as<uint8_t>() + i * fb, frames[f0 + i], fb, hipMemcpyHostToDevice, c->cin) !=
-          hipSuccess)
-        return MYYUV_E_HIP;
-    if (hipEventRecord(c->pev[0][sl], c->cin) != hipSuccess) return MYYUV_E_HIP;
-    PIPE_TRACE("pipe c chunk %u: uploads queued\n", k);
-    // kernels (output slot free once chunk k-2's payloads are back)
-    if (hipStreamWaitEvent(s, c->pev[0][sl], 0) != hipSuccess ||
-        (k >= 2 && hipStreamWaitEvent(s, c->pev[2][sl], 0) != hipSuccess))
-      return MYYUV_E_HIP;
-    unsigned long long* perr = c->perr[sl].as<unsigned long long>();
-    if ((e = launch_compress(c, GK, c->pin[sl].p, c->pout[sl].p, dcap, c->psz[sl].as<uint32_t>(), s, perr)))
-      return e;
-    if (hipMemcpyAsync(c->hsz + sl * kPipeMaxChunk, c->psz[sl].p, (size_t)n * 4, hipMemcpyDeviceToHost, s) !=
-            hipSuccess ||
-        hipMemcpyAsync(c->herr + sl, perr, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemsetAsync(perr, 0xFF, 8, s) != hipSuccess || hipEventRecord(c->pev[1][sl], s) != hipSuccess)
-      return MYYUV_E_HIP;
-    if (k >= 1 && (e = finish(k - 1))) return e;
-  }
-  if ((e = finish(nchunks - 1))) return e;
-  PIPE_TRACE("pipe c: wait downloads\n");
-  if (hipStreamSynchronize(c->cout) != hipSuccess) return MYYUV_E_HIP;
-  PIPE_TRACE("pipe c: done\n");
-  if (c->prof) drain_profile(c);
-  return 0;
+  return pipe_frames(
+      c, 'c', nf, w, h, q, fb, dcap, nullptr,
+      [&](HostPipe& P, uint32_t sl, uint32_t f0, uint32_t n) {
+        int e = 0;
+        for (uint32_t i = 0; i < n && !e; i++)
+          e = h2d(P.pin[sl].as<uint8_t>() + i * fb, frames[f0 + i], fb, P.cin);
+        return e;
+      },
+      [&](HostPipe& P, const FrameGeom& GK, uint32_t sl, unsigned long long* perr, hipStream_t s) {
+        if (int e = launch_compress(c, GK, P.pin[sl].p, P.pout[sl].p, dcap, P.psz[sl].as<uint32_t>(), s, perr))
+          return e;
+        return hipMemcpyAsync(P.sizes(sl), P.psz[sl].p, (size_t)GK.nframes * 4, hipMemcpyDeviceToHost, s) == hipSuccess
+                   ? 0
+                   : MYYUV_E_HIP;
+      },
+      [&](HostPipe& P, uint32_t sl, uint32_t f0, uint32_t n) {
+        for (uint32_t i = 0; i < n; i++) {
+          const uint32_t size = P.sizes(sl)[i];
+          sizes[f0 + i] = size;
+          uint8_t* dst = alloc(user, f0 + i, size);
+          if (!dst) return MYYUV_E_CAPACITY;
+          if (hipMemcpyAsync(dst, P.pout[sl].as<uint8_t>() + (size_t)i * dcap, size, hipMemcpyDeviceToHost, P.cout) !=
+              hipSuccess)
+            return MYYUV_E_HIP;
+        }
+        return 0;
+      });
 }
 
 int decompress_frames(myyuv_hip_ctx* c, const uint8_t* const* payloads, const uint32_t* psizes, uint32_t nf,
                       uint32_t w, uint32_t h, const uint8_t q[3], uint8_t* const* frames, int64_t* bad_block) {
-  FrameGeom G;
-  int e = make_geom(w, h, G);
-  if (e) return e;
   const size_t fb = (size_t)w * h * 3 / 2;
   uint32_t icap = 4;  // device slot per stream: the longest, 4-aligned
   for (uint32_t f = 0; f < nf; f++) icap = std::max(icap, (psizes[f] + 3u) & ~3u);
-  const uint32_t B = std::min(pipe_chunk(nf, fb + icap), launch_frames(G, c->launch_blocks));
-  FrameGeom GB = G;
-  if ((e = set_batch(GB, B))) return e;
-  hipStream_t s = c->stream;
-  StreamOrder so(c, s);
-  if ((e = pipe_init(c)) || (e = reserve(c, GB)) || (e = set_qtables(c, q, s))) return e;
-  for (int k = 0; k < 2; k++)
-    if (c->pin[k].grow((size_t)icap * B) || c->pout[k].grow(fb * B)) return MYYUV_E_HIP;
-  PipeDrain drain{c};
-  const uint32_t nchunks = ceil_div(nf, B);
-  auto finish = [&](uint32_t k) -> int {
-    const uint32_t sl = k & 1, f0 = k * B, n = std::min(B, nf - f0);
-    if (hipEventSynchronize(c->pev[1][sl]) != hipSuccess) return MYYUV_E_HIP;
-    if (int ce = chunk_err(c->herr[sl], f0, G.cum[3], bad_block)) return ce;
-    for (uint32_t i = 0; i < n; i++)
-      if (hipMemcpyAsync(frames[f0 + i], c->pout[sl].as<uint8_t>() + i * fb, fb, hipMemcpyDeviceToHost, c->cout) !=
-          hipSuccess)
-        return MYYUV_E_HIP;
-    return hipEventRecord(c->pev[2][sl], c->cout) == hipSuccess ? 0 : MYYUV_E_HIP;
-  };
-  for (uint32_t k = 0; k < nchunks; k++) {
-    const uint32_t sl = k & 1, f0 = k * B, n = std::min(B, nf - f0);
-    FrameGeom GK = G;
-    if ((e = set_batch(GK, n))) return e;
-    if (k >= 2 && hipStreamWaitEvent(c->cin, c->pev[1][sl], 0) != hipSuccess) return MYYUV_E_HIP;
-    uint8_t* slot = c->pin[sl].as<uint8_t>();
-    for (uint32_t i = 0; i < n; i++) {
-      const uint32_t sz = psizes[f0 + i], cap_i = (sz + 3u) & ~3u;
-      // the stream's last word zero-padded (the scan reads whole words), then the bytes
-      if ((cap_i >= 4 && hipMemsetAsync(slot + (size_t)i * icap + cap_i - 4, 0, 4, c->cin) != hipSuccess) ||
-          hipMemcpyAsync(slot + (size_t)i * icap, payloads[f0 + i], sz, hipMemcpyHostToDevice, c->cin) != hipSuccess)
-        return MYYUV_E_HIP;
-    }
-    if (hipMemcpyAsync(c->psz[sl].p, psizes + f0, (size_t)n * 4, hipMemcpyHostToDevice, c->cin) != hipSuccess ||
-        hipEventRecord(c->pev[0][sl], c->cin) != hipSuccess)
-      return MYYUV_E_HIP;
-    if (hipStreamWaitEvent(s, c->pev[0][sl], 0) != hipSuccess ||
-        (k >= 2 && hipStreamWaitEvent(s, c->pev[2][sl], 0) != hipSuccess))
-      return MYYUV_E_HIP;
-    unsigned long long* perr = c->perr[sl].as<unsigned long long>();
-    if ((e = launch_decompress(c, GK, slot, c->psz[sl].as<const uint32_t>(), icap, c->pout[sl].p, s, perr)))
-      return e;
-    if (hipMemcpyAsync(c->herr + sl, perr, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemsetAsync(perr, 0xFF, 8, s) != hipSuccess || hipEventRecord(c->pev[1][sl], s) != hipSuccess)
-      return MYYUV_E_HIP;
-    if (k >= 1 && (e = finish(k - 1))) return e;
-  }
-  if ((e = finish(nchunks - 1))) return e;
-  if (hipStreamSynchronize(c->cout) != hipSuccess) return MYYUV_E_HIP;
-  if (c->prof) drain_profile(c);
-  return 0;
+  return pipe_frames(
+      c, 'd', nf, w, h, q, icap, fb, bad_block,
+      [&](HostPipe& P, uint32_t sl, uint32_t f0, uint32_t n) {
+        uint8_t* slot = P.pin[sl].as<uint8_t>();
+        for (uint32_t i = 0; i < n; i++) {
+          const uint32_t sz = psizes[f0 + i], cap_i = (sz + 3u) & ~3u;
+          // the stream's last word zero-padded (the scan reads whole words), then the bytes
+          if ((cap_i >= 4 && hipMemsetAsync(slot + (size_t)i * icap + cap_i - 4, 0, 4, P.cin) != hipSuccess) ||
+              h2d(slot + (size_t)i * icap, payloads[f0 + i], sz, P.cin))
+            return MYYUV_E_HIP;
+        }
+        return h2d(P.psz[sl].p, psizes + f0, (size_t)n * 4, P.cin);
+      },
+      [&](HostPipe& P, const FrameGeom& GK, uint32_t sl, unsigned long long* perr, hipStream_t s) {
+        return launch_decompress(c, GK, P.pin[sl].p, P.psz[sl].as<const uint32_t>(), icap, P.pout[sl].p, s, perr);
+      },
+      [&](HostPipe& P, uint32_t sl, uint32_t f0, uint32_t n) {
+        for (uint32_t i = 0; i < n; i++)
+          if (hipMemcpyAsync(frames[f0 + i], P.pout[sl].as<uint8_t>() + i * fb, fb, hipMemcpyDeviceToHost, P.cout) !=
+              hipSuccess)
+            return MYYUV_E_HIP;
+        return 0;
+      });
 }
 
 struct SlotAlloc {
@@ -1228,12 +986,6 @@ uint8_t* slot_alloc(void* user, uint32_t frame, uint32_t size) {
   return size <= a->cap ? a->base + (size_t)frame * a->cap : nullptr;
 }
 
-int check_q(const uint8_t q[3]) {
-  for (int p = 0; p < 3; p++)
-    if (q[p] < 1 || q[p] > 100) return MYYUV_E_QUALITY;
-  return 0;
-}
-
 }  // namespace
 
 int myyuv_gpu_dct_compress_frames(myyuv_hip_handle c, const uint8_t* const* frames, uint32_t nframes, uint32_t w,
@@ -1243,8 +995,6 @@ int myyuv_gpu_dct_compress_frames(myyuv_hip_handle c, const uint8_t* const* fram
   for (uint32_t f = 0; f < nframes; f++)
     if (!frames[f]) return MYYUV_E_ARG;
   if (int e = check_q(q)) return e;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
   return compress_frames(c, frames, nframes, w, h, q, alloc, user, sizes);
 }
 
@@ -1257,8 +1007,6 @@ int myyuv_gpu_dct_compress_batch(myyuv_hip_handle c, const uint8_t* iyuv, uint32
   std::vector<const uint8_t*> fr(nframes);
   for (uint32_t f = 0; f < nframes; f++) fr[f] = iyuv + f * fb;
   SlotAlloc a{payloads, cap};
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
   return compress_frames(c, fr.data(), nframes, w, h, q, slot_alloc, &a, sizes);
 }
 
@@ -1274,8 +1022,6 @@ int myyuv_gpu_dct_decompress_frames(myyuv_hip_handle c, const uint8_t* const* pa
   // call's order), frame by frame
   for (uint32_t f = 0; f < nframes; f++)
     if (int e = host_parse_headers(payloads[f], sizes[f])) return e;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
   return decompress_frames(c, payloads, sizes, nframes, w, h, q, frames, bad_block);
 }
 
@@ -1323,253 +1069,6 @@ int myyuv_hip_kernel_stats(myyuv_hip_handle c, double ms[MYYUV_K_COUNT],
   for (int k = 0; k < MYYUV_K_COUNT; k++) {
     ms[k] = c->ms[k];
     launches[k] = c->launches[k];
-  }
-  return 0;
-}
-
-// Diagnostic builds: per-wave stage cycles of the CAP=8 pass (n waves).
-int myyuv_debug_k2_fstamps(uint32_t* out, uint32_t n) {
-#ifdef MYYUV_STAMPS
-  if (n > 8192) n = 8192;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k2_fstamps), (size_t)n * 32) == hipSuccess ? 0 : MYYUV_E_HIP;
-#else
-  (void)out;
-  (void)n;
-  return MYYUV_E_ARG;
-#endif
-}
-
-// Diagnostic builds (-DMYYUV_STAMPS): K2's per-wave window phases of the last
-// launch, n waves x 8 words (k_huff_encode.hip g_k2_win; word 7 = 1 for a
-// wave that ran), then zeroed.
-int myyuv_debug_k2_win(uint32_t* out, uint32_t n) {
-#ifdef MYYUV_STAMPS
-  if (n > 65536) n = 65536;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k2_win), (size_t)n * 32) != hipSuccess) return MYYUV_E_HIP;
-  std::vector<uint32_t> zero((size_t)n * 8, 0u);
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_k2_win), zero.data(), (size_t)n * 32) == hipSuccess ? 0 : MYYUV_E_HIP;
-#else
-  (void)out;
-  (void)n;
-  return MYYUV_E_ARG;
-#endif
-}
-
-// Diagnostic builds: per-block phase cycles of the wave encoder (n blocks).
-int myyuv_debug_k2_wstamps(uint32_t* out, uint32_t n) {
-#ifdef MYYUV_STAMPS
-  if (n > 65536) n = 65536;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k2_wstamps), (size_t)n * 32) == hipSuccess ? 0 : MYYUV_E_HIP;
-#else
-  (void)out;
-  (void)n;
-  return MYYUV_E_ARG;
-#endif
-}
-
-// Diagnostic builds (-DMYYUV_STAMPS): the fused decoder's per-phase wave
-// cycles of the last launch, n waves x 8 words (k_huff_decode.hip
-// g_dec_wstamps; word 7 = 1 for a wave that ran), then zeroed.
-int myyuv_debug_dec_stamps(uint32_t* out, uint32_t n) {
-#ifdef MYYUV_STAMPS
-  if (n > 65536) n = 65536;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dec_wstamps), (size_t)n * 32) != hipSuccess) return MYYUV_E_HIP;
-  std::vector<uint32_t> zero((size_t)n * 8, 0u);
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_dec_wstamps), zero.data(), (size_t)n * 32) == hipSuccess ? 0 : MYYUV_E_HIP;
-#else
-  (void)out;
-  (void)n;
-  return MYYUV_E_ARG;
-#endif
-}
-
-// Diagnostic: stop launching the kernels whose bit (1 << MYYUV_K_*) is set,
-// to measure each kernel's share of a pipelined run.  The buffers keep what the
-// last real launch wrote, so repeating identical frames still decodes.
-int myyuv_debug_skip_kernels(myyuv_hip_handle c, uint32_t mask) {
-  if (!c) return MYYUV_E_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->skip = mask;
-  return 0;
-}
-
-// Diagnostic builds (-DMYYUV_STAMPS): summed per-stage wave cycles of K2
-// since the last call; returns MYYUV_E_ARG in normal builds.
-int myyuv_debug_k2_stamps(unsigned long long out[40]) {
-#ifdef MYYUV_STAMPS
-  unsigned long long zero[40] = {0};
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k2_stamps), 320) != hipSuccess) return MYYUV_E_HIP;
-  if (hipMemcpyToSymbol(HIP_SYMBOL(g_k2_stamps), zero, 320) != hipSuccess) return MYYUV_E_HIP;
-  return 0;
-#else
-  (void)out;
-  return MYYUV_E_ARG;
-#endif
-}
-
-// Diagnostic: the coefficient image of the last compress/decompress (natural
-// order, the quad layout of codec_common.hpp), n blocks, as int16[n][64].
-int myyuv_debug_coef(myyuv_hip_handle c, int16_t* out, uint32_t n) {
-  if (!c || !out) return MYYUV_E_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  const size_t nq = (size_t)ceil_div(n, kWave) * kCoefQuadsPerWave;
-  if (nq * 16 > c->coef.n) return MYYUV_E_ARG;
-  if (n > c->rmask.n) return MYYUV_E_ARG;
-  std::vector<uint4> img(nq);
-  std::vector<uint8_t> rm(n);
-  if (hipStreamSynchronize(c->stream) != hipSuccess ||
-      hipMemcpy(img.data(), c->coef.p, nq * 16, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(rm.data(), c->rmask.p, n, hipMemcpyDeviceToHost) != hipSuccess)
-    return MYYUV_E_HIP;
-  for (uint32_t b = 0; b < n; b++)
-    for (uint32_t q = 0; q < 8; q++) {  // rows outside the row mask are zero (not stored)
-      if ((rm[b] >> q) & 1u)
-        std::memcpy(out + (size_t)b * 64 + q * 8, &img[coef_quad(b, q)], 16);
-      else
-        std::memset(out + (size_t)b * 64 + q * 8, 0, 16);
-    }
-  return 0;
-}
-
-// Diagnostic: the tile-info guard band.  arm != 0 fills the kWinTilesBig x
-// kTInfoWords words after tile ntiles (the batch's last tile) with a canary;
-// arm == 0 returns in *changed how many of them no longer hold it (a kernel
-// wrote past the batch's tiles: the K2 window overrun of round 5's advice).
-int myyuv_debug_tinfo_guard(myyuv_hip_handle c, uint32_t ntiles, int arm, uint32_t* changed) {
-  if (!c) return MYYUV_E_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  constexpr uint32_t kGuardWords = kWinTilesBig * kTInfoWords;
-  constexpr uint32_t kCanary = 0xA5C3E1F7u;
-  const size_t off = (size_t)ntiles * kTInfoWords * 4;
-  if (off + kGuardWords * 4 > c->tinfo.n) return MYYUV_E_ARG;
-  std::vector<uint32_t> w(kGuardWords, kCanary);
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return MYYUV_E_HIP;
-  uint8_t* p = static_cast<uint8_t*>(c->tinfo.p) + off;
-  if (arm) return hipMemcpy(p, w.data(), kGuardWords * 4, hipMemcpyHostToDevice) == hipSuccess ? 0 : MYYUV_E_HIP;
-  if (!changed) return MYYUV_E_ARG;
-  if (hipMemcpy(w.data(), p, kGuardWords * 4, hipMemcpyDeviceToHost) != hipSuccess) return MYYUV_E_HIP;
-  uint32_t n = 0;
-  for (uint32_t v : w) n += v != kCanary;
-  *changed = n;
-  return 0;
-}
-
-// ---- block-level KAT entry points -----------------------------------------
-int myyuv_gpu_fdct_blocks(myyuv_hip_handle c, const uint8_t* px, uint32_t nblocks,
-                          const float qtable[64], int16_t* coef_zz) {
-  if (!c || !px || !qtable || !coef_zz || nblocks == 0) return MYYUV_E_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  hipStream_t s = c->stream;
-  StreamOrder so(c, s);
-  // one plane of width 8 (one block per block-row); planes 1, 2 empty
-  FrameGeom G;
-  std::memset(&G, 0, sizeof(G));
-  G.pw[0] = 8;
-  G.ph[0] = 8 * nblocks;
-  G.bw[0] = 1;
-  G.bmag[0] = block_magic(1);
-  G.cum[1] = G.cum[2] = G.cum[3] = nblocks;
-  G.ucum[1] = G.ucum[2] = G.ucum[3] = ceil_div(nblocks, kXfUnit);
-  G.nframes = 1;
-  G.fbytes = nblocks * 64;
-  G.umag = block_magic(G.ucum[3]);
-  QTables t;
-  std::memset(&t, 0, sizeof(t));
-  std::memcpy(t.q[0], qtable, 256);
-  finish_qtables(t, 1);
-  if (reserve(c, G) || c->frame.grow((size_t)nblocks * 64) || c->qtd.grow(sizeof(QTables)))
-    return MYYUV_E_HIP;
-  c->q_valid = false;
-  if (hipStreamSynchronize(s) != hipSuccess ||
-      hipMemcpy(c->qtd.p, &t, sizeof(t), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->frame.p, px, (size_t)nblocks * 64, hipMemcpyHostToDevice) != hipSuccess)
-    return MYYUV_E_HIP;
-  if (launch_fdct(c, G, c->frame.as<const uint8_t>(), c->qtd.as<const QTables>(), nullptr, s))
-    return MYYUV_E_HIP;
-  std::vector<uint32_t> words((size_t)ceil_div(nblocks, kWave) * kCoefQuadsPerWave * 4);
-  std::vector<uint8_t> rm(nblocks);
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(words.data(), c->coef.p, words.size() * 4, hipMemcpyDeviceToHost, s) !=
-          hipSuccess ||
-      hipMemcpyAsync(rm.data(), c->rmask.p, nblocks, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return MYYUV_E_HIP;
-  for (uint32_t g = 0; g < nblocks; g++) {
-    int16_t nat[64];
-    for (uint32_t c4 = 0; c4 < 8; c4++) {  // rows K1 left out of the image (mask bit clear) are zero
-      if ((rm[g] >> c4) & 1u)
-        std::memcpy(nat + 8 * c4, &words[(size_t)coef_quad(g, c4) * 4], 16);
-      else
-        std::memset(nat + 8 * c4, 0, 16);
-    }
-    for (int z = 0; z < 64; z++) coef_zz[(size_t)g * 64 + z] = nat[kZigzag[z]];
-  }
-  return 0;
-}
-
-int myyuv_gpu_huff_encode_blocks(myyuv_hip_handle c, const int16_t* coef_zz, uint32_t nblocks,
-                                 uint8_t* chunks160, uint8_t* sizes) {
-  if (!c || !coef_zz || !chunks160 || !sizes || nblocks == 0) return MYYUV_E_ARG;
-  // the chunk format carries 11-bit symbols (pack11bit, Huffman.cpp:36-52);
-  // K1 never produces others (DCT.cpp:276 asserts the range)
-  for (size_t i = 0; i < (size_t)nblocks * 64; i++)
-    if (coef_zz[i] < -1024 || coef_zz[i] > 1023) return MYYUV_E_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  hipStream_t s = c->stream;
-  StreamOrder so(c, s);
-  FrameGeom G;
-  std::memset(&G, 0, sizeof(G));
-  G.cum[1] = G.cum[2] = G.cum[3] = nblocks;  // one plane of nblocks blocks
-  G.tcum[1] = G.tcum[2] = G.tcum[3] = ceil_div(nblocks, kK2Group);
-  G.nframes = 1;
-  if (reserve(c, G)) return MYYUV_E_HIP;
-  const uint32_t nwaves = ceil_div(nblocks, kWave);
-  // host-side relayout into K1's output format: natural-order quads
-  // and the per-block words K1 writes for K2's classification (binfo_word;
-  // every row marked present)
-  std::vector<uint32_t> words((size_t)nwaves * kCoefQuadsPerWave * 4, 0u), info(nblocks);
-  for (uint32_t g = 0; g < nblocks; g++) {
-    int16_t nat[64];
-    uint32_t nnz = 0, msz = 0;
-    for (int z = 0; z < 64; z++) {
-      const int16_t v = coef_zz[(size_t)g * 64 + z];
-      nat[kZigzag[z]] = v;
-      if (v != 0) {
-        nnz++;
-        msz = (uint32_t)z + 1u;
-      }
-    }
-    for (uint32_t c4 = 0; c4 < 8; c4++)
-      std::memcpy(&words[(size_t)coef_quad(g, c4) * 4], nat + 8 * c4, 16);
-    info[g] = binfo_word(0xFFu, msz, class_of(nnz, msz), (uint32_t)(uint16_t)nat[0]);
-  }
-  if (hipMemcpy(c->coef.p, words.data(), words.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->binfo.p, info.data(), (size_t)nblocks * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemsetAsync(c->rmask.p, 0xFF, nblocks, s) != hipSuccess ||  // every row present
-      hipMemsetAsync(c->work.p, 0, 4, s) != hipSuccess)  // K1 zeroes it in the codec path
-    return MYYUV_E_HIP;
-  if (launch_huff_encode(c, G, s)) return MYYUV_E_HIP;
-  // K2's hand-off (codec_common.hpp): per tile the waves' dense runs, the
-  // chunks of blocks with more than 8 symbols in their own slots
-  const uint32_t ntile = G.tcum[3];
-  std::vector<uint8_t> stage((size_t)win_tiles_alloc(ntile) * kTileCap), oslots((size_t)nblocks * kMaxChunk);
-  std::vector<uint32_t> soff(nblocks);
-  if (hipMemcpyAsync(stage.data(), c->stage.p, stage.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(oslots.data(), c->oslots.p, oslots.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(soff.data(), c->srcoff.p, (size_t)nblocks * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(sizes, c->sizes.p, nblocks, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return MYYUV_E_HIP;
-  for (uint32_t g = 0; g < nblocks; g++) {
-    uint8_t* dst = chunks160 + (size_t)g * kMaxChunk;
-    std::memset(dst, 0, kMaxChunk);
-    const uint8_t* src = soff[g] == kSrcOverflow ? oslots.data() + (size_t)g * kMaxChunk
-                                                 : stage.data() + (size_t)win_first_tile(g / kK2Group, k2_win(G.nframes * ntile)) * kTileCap + soff[g];
-    std::memcpy(dst, src, sizes[g]);
   }
   return 0;
 }
