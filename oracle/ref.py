@@ -35,6 +35,12 @@ def lib(variant="omp"):
     return _LIBS[variant]
 
 
+def has(symbol, variant="serial"):
+    """Whether the built library exports `symbol`: an oracle/_ref built from
+    an older ref_harness.cpp lacks the entry points added since."""
+    return available(variant) and hasattr(lib(variant), symbol)
+
+
 def _p(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
@@ -79,6 +85,19 @@ def bench(iyuv, w, h, q, iters, variant="omp"):
     if rc:
         raise RefError(L.ref_last_error().decode())
     return tc.value, td.value
+
+
+def huff_encode_block(coef, variant="serial"):
+    """One block's chunk from the reference's own Huffman::fromData / dump
+    (ref_harness.cpp): 64 int16 in natural order, as oracle.huff_encode_block."""
+    L = lib(variant)
+    L.ref_huff_encode_block.argtypes = [ctypes.POINTER(ctypes.c_int16), ctypes.POINTER(ctypes.c_uint8)]
+    c = np.ascontiguousarray(coef, np.int16).reshape(64)
+    out = np.zeros(256, np.uint8)
+    n = L.ref_huff_encode_block(c.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), _p(out))
+    if n < 0:
+        raise RefError(L.ref_last_error().decode())
+    return out[:n].tobytes()
 
 
 def bmp_to_iyuv(path, variant="serial"):

@@ -9,8 +9,10 @@
 // Calls only the reference's public surface: myyuv::YUV (myyuv_yuv.hpp:37-350),
 // YUV::compress / YUV::decompress (myyuv_yuv.cpp:454-483), which dispatch through
 // YUV::compress_map / decompress_map to myyuvDCT::compress_DCT_planar /
-// decompress_DCT_planar (DCT.cpp:371-488).
+// decompress_DCT_planar (DCT.cpp:371-488); and, for one block's entropy coding
+// alone, myyuvDCT::Huffman::fromData / dump (myyuv_DCT/Huffman.hpp:66, :80).
 #include <myyuv.hpp>
+#include <myyuv_DCT/Huffman.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -132,6 +134,24 @@ int ref_bmp_to_iyuv(const char* path, uint8_t* out, uint32_t cap, uint32_t* w, u
   } catch (const std::exception& e) {
     g_last_error = e.what();
     return 1;
+  }
+}
+
+// One block through the reference's entropy coder alone: the public
+// myyuvDCT::Huffman::fromData (64 coefficients in natural order, Huffman.cpp
+// applies the zig-zag) and dump.  Writes the chunk (at most 255 bytes) to out
+// and returns its size, or -1 on an exception.
+int ref_huff_encode_block(const int16_t coef[64], uint8_t* out) {
+  try {
+    uint8_t* data = nullptr;
+    uint8_t size = 0;
+    myyuvDCT::Huffman::fromData(coef).dump(data, size);
+    std::memcpy(out, data, size);
+    delete[] data;
+    return size;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return -1;
   }
 }
 

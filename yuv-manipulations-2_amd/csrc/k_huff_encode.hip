@@ -983,6 +983,8 @@ namespace {
 #ifndef MYYUV_K2_MSZ_SPLIT
 #define MYYUV_K2_MSZ_SPLIT 3
 #endif
+static_assert(MYYUV_K2_MSZ_SPLIT == 2 || MYYUV_K2_MSZ_SPLIT == 3,
+              "MYYUV_K2_MSZ_SPLIT: sort_key has bucket tables for 2 and 3 splits only");
 constexpr uint32_t kMszBuckets = MYYUV_K2_MSZ_SPLIT + 1;
 constexpr uint32_t kOvfKey = 1 + (kClassOvf - 1) * kMszBuckets;
 constexpr uint32_t kKeys = kOvfKey + 2;

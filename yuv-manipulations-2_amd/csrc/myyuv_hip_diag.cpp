@@ -50,6 +50,89 @@ int read_coef(myyuv_hip_ctx* c, uint32_t n, int16_t* out) {
   return 0;
 }
 
+// K2 and its overflow passes (launch_huff_encode) over nframes x nblocks
+// coefficient blocks given in zig-zag order: a batch of nframes one-plane
+// frames of nblocks blocks each (block_geom; nframes = 1: a single frame, with
+// the single-frame gates).  chunks160 / sizes: per block, batch order.
+// counts (may be null): work[0], the length of K2's overflow list; work[1],
+// how many of them the CAP-16 tier listed again (0 when it did not run); and
+// the chunk bytes the launch booked in its tiles' info words, which K4 places
+// the chunks by: the overflow passes' (word 0; a block encoded by two passes
+// is booked twice) and K2's dense runs' (words 1..4), each summed over the tiles.
+int huff_encode_blocks(myyuv_hip_ctx* c, const int16_t* coef_zz, uint32_t nblocks, uint32_t nframes,
+                       uint8_t* chunks160, uint8_t* sizes, uint32_t counts[4]) {
+  if (!c || !coef_zz || !chunks160 || !sizes || nblocks == 0 || nframes == 0) return MYYUV_E_ARG;
+  if ((uint64_t)nblocks * nframes > kMaxLaunchBlocks) return MYYUV_E_ARG;
+  const uint32_t ntotal = nblocks * nframes;
+  // the chunk format carries 11-bit symbols (pack11bit, Huffman.cpp:36-52);
+  // K1 never produces others (DCT.cpp:276 asserts the range)
+  for (size_t i = 0; i < (size_t)ntotal * 64; i++)
+    if (coef_zz[i] < -1024 || coef_zz[i] > 1023) return MYYUV_E_ARG;
+  Entry en(c);
+  hipStream_t s = en.s;
+  FrameGeom G = block_geom(nblocks);
+  G.nframes = nframes;
+  if (reserve(c, G)) return MYYUV_E_HIP;
+  const uint32_t nwaves = ceil_div(ntotal, kWave);
+  // host-side relayout into K1's output format: natural-order quads
+  // and the per-block words K1 writes for K2's classification (binfo_word;
+  // every row marked present)
+  std::vector<uint32_t> words((size_t)nwaves * kCoefQuadsPerWave * 4, 0u), info(ntotal);
+  for (uint32_t g = 0; g < ntotal; g++) {
+    int16_t nat[64];
+    uint32_t nnz = 0, msz = 0;
+    for (int z = 0; z < 64; z++) {
+      const int16_t v = coef_zz[(size_t)g * 64 + z];
+      nat[kZigzag[z]] = v;
+      if (v != 0) {
+        nnz++;
+        msz = (uint32_t)z + 1u;
+      }
+    }
+    for (uint32_t c4 = 0; c4 < 8; c4++)
+      std::memcpy(&words[(size_t)coef_quad(g, c4) * 4], nat + 8 * c4, 16);
+    info[g] = binfo_word(0xFFu, msz, class_of(nnz, msz), (uint32_t)(uint16_t)nat[0]);
+  }
+  if (hipMemcpy(c->coef.p, words.data(), words.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(c->binfo.p, info.data(), (size_t)ntotal * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemsetAsync(c->rmask.p, 0xFF, ntotal, s) != hipSuccess ||  // every row present
+      // work[0]: K1 zeroes it in the codec path; work[1]: launch_overflow
+      // zeroes it when the tier runs, here also when it does not (`counts`)
+      hipMemsetAsync(c->work.p, 0, 8, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  if (launch_huff_encode(c, G, s)) return MYYUV_E_HIP;
+  // K2's hand-off (codec_common.hpp): per tile the waves' dense runs, the
+  // chunks of blocks with more than 8 symbols in their own slots
+  const uint32_t ntile = nframes * G.tcum[3];
+  std::vector<uint8_t> stage((size_t)win_tiles_alloc(ntile) * kTileCap), oslots((size_t)ntotal * kMaxChunk);
+  std::vector<uint32_t> soff(ntotal);
+  std::vector<uint32_t> ti((size_t)ntile * kTInfoWords);
+  uint32_t cnt[4] = {0, 0, 0, 0};
+  if (hipMemcpyAsync(stage.data(), c->stage.p, stage.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(oslots.data(), c->oslots.p, oslots.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(soff.data(), c->srcoff.p, (size_t)ntotal * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(sizes, c->sizes.p, ntotal, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(cnt, c->work.p, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(ti.data(), c->tinfo.p, ti.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return MYYUV_E_HIP;
+  for (uint32_t t = 0; t < ntile; t++) {
+    cnt[2] += ti[(size_t)t * kTInfoWords];
+    for (uint32_t w = 1; w <= kK2Group / kWave; w++) cnt[3] += ti[(size_t)t * kTInfoWords + w];
+  }
+  if (counts) std::memcpy(counts, cnt, sizeof(cnt));
+  const uint32_t W = k2_win(ntile);
+  for (uint32_t g = 0; g < ntotal; g++) {
+    uint8_t* dst = chunks160 + (size_t)g * kMaxChunk;
+    std::memset(dst, 0, kMaxChunk);
+    const uint8_t* src = soff[g] == kSrcOverflow
+                             ? oslots.data() + (size_t)g * kMaxChunk
+                             : stage.data() + (size_t)win_first_tile(tile_of_block(G, g), W) * kTileCap + soff[g];
+    std::memcpy(dst, src, std::min<uint32_t>(sizes[g], kMaxChunk));  // (a size no pass wrote may hold anything)
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -147,59 +230,28 @@ int myyuv_gpu_fdct_blocks(myyuv_hip_handle c, const uint8_t* px, uint32_t nblock
 
 int myyuv_gpu_huff_encode_blocks(myyuv_hip_handle c, const int16_t* coef_zz, uint32_t nblocks,
                                  uint8_t* chunks160, uint8_t* sizes) {
-  if (!c || !coef_zz || !chunks160 || !sizes || nblocks == 0) return MYYUV_E_ARG;
-  // the chunk format carries 11-bit symbols (pack11bit, Huffman.cpp:36-52);
-  // K1 never produces others (DCT.cpp:276 asserts the range)
-  for (size_t i = 0; i < (size_t)nblocks * 64; i++)
-    if (coef_zz[i] < -1024 || coef_zz[i] > 1023) return MYYUV_E_ARG;
-  Entry en(c);
-  hipStream_t s = en.s;
-  const FrameGeom G = block_geom(nblocks);
-  if (reserve(c, G)) return MYYUV_E_HIP;
-  const uint32_t nwaves = ceil_div(nblocks, kWave);
-  // host-side relayout into K1's output format: natural-order quads
-  // and the per-block words K1 writes for K2's classification (binfo_word;
-  // every row marked present)
-  std::vector<uint32_t> words((size_t)nwaves * kCoefQuadsPerWave * 4, 0u), info(nblocks);
-  for (uint32_t g = 0; g < nblocks; g++) {
-    int16_t nat[64];
-    uint32_t nnz = 0, msz = 0;
-    for (int z = 0; z < 64; z++) {
-      const int16_t v = coef_zz[(size_t)g * 64 + z];
-      nat[kZigzag[z]] = v;
-      if (v != 0) {
-        nnz++;
-        msz = (uint32_t)z + 1u;
-      }
-    }
-    for (uint32_t c4 = 0; c4 < 8; c4++)
-      std::memcpy(&words[(size_t)coef_quad(g, c4) * 4], nat + 8 * c4, 16);
-    info[g] = binfo_word(0xFFu, msz, class_of(nnz, msz), (uint32_t)(uint16_t)nat[0]);
-  }
-  if (hipMemcpy(c->coef.p, words.data(), words.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->binfo.p, info.data(), (size_t)nblocks * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemsetAsync(c->rmask.p, 0xFF, nblocks, s) != hipSuccess ||  // every row present
-      hipMemsetAsync(c->work.p, 0, 4, s) != hipSuccess)  // K1 zeroes it in the codec path
-    return MYYUV_E_HIP;
-  if (launch_huff_encode(c, G, s)) return MYYUV_E_HIP;
-  // K2's hand-off (codec_common.hpp): per tile the waves' dense runs, the
-  // chunks of blocks with more than 8 symbols in their own slots
-  const uint32_t ntile = G.tcum[3];
-  std::vector<uint8_t> stage((size_t)win_tiles_alloc(ntile) * kTileCap), oslots((size_t)nblocks * kMaxChunk);
-  std::vector<uint32_t> soff(nblocks);
-  if (hipMemcpyAsync(stage.data(), c->stage.p, stage.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(oslots.data(), c->oslots.p, oslots.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(soff.data(), c->srcoff.p, (size_t)nblocks * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(sizes, c->sizes.p, nblocks, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return MYYUV_E_HIP;
-  for (uint32_t g = 0; g < nblocks; g++) {
-    uint8_t* dst = chunks160 + (size_t)g * kMaxChunk;
-    std::memset(dst, 0, kMaxChunk);
-    const uint8_t* src = soff[g] == kSrcOverflow ? oslots.data() + (size_t)g * kMaxChunk
-                                                 : stage.data() + (size_t)win_first_tile(g / kK2Group, k2_win(G.nframes * ntile)) * kTileCap + soff[g];
-    std::memcpy(dst, src, sizes[g]);
-  }
+  return huff_encode_blocks(c, coef_zz, nblocks, 1, chunks160, sizes, nullptr);
+}
+
+// Diagnostic: myyuv_gpu_huff_encode_blocks over a batch of nframes frames of
+// nblocks blocks each (coef_zz, chunks160, sizes: nframes x nblocks entries),
+// returning the launch's two overflow list lengths and its booked overflow
+// and dense chunk bytes in counts[0..3] (huff_encode_blocks above).
+int myyuv_debug_huff_encode_blocks(myyuv_hip_handle c, const int16_t* coef_zz, uint32_t nblocks, uint32_t nframes,
+                                   uint8_t* chunks160, uint8_t* sizes, uint32_t counts[4]) {
+  if (!counts) return MYYUV_E_ARG;
+  return huff_encode_blocks(c, coef_zz, nblocks, nframes, chunks160, sizes, counts);
+}
+
+// Diagnostic: the constants the overflow regimes switch on (codec_common.hpp),
+// so that tests place list lengths at them without restating the values:
+// kR16GateSingle, kR16Gate, kWaveEncodeLimit, kBatchWaveLimit, kK2Group, the
+// blocks of one K2 window (kWinTiles tiles), and kOvfNub.
+int myyuv_debug_k2_constants(uint32_t out[7]) {
+  if (!out) return MYYUV_E_ARG;
+  const uint32_t v[7] = {kR16GateSingle, kR16Gate, kWaveEncodeLimit, kBatchWaveLimit, kK2Group,
+                         kWinTiles * kK2Group, kOvfNub};
+  std::memcpy(out, v, sizeof(v));
   return 0;
 }
 

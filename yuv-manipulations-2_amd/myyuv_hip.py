@@ -113,6 +113,9 @@ def load():
     L.myyuv_gpu_dct_compress_frames.argtypes = [vp, ctypes.POINTER(vp), u32, u32, u32, u8p, PAYLOAD_ALLOC, vp,
                                                 ctypes.POINTER(u32)]
     L.myyuv_debug_tinfo_guard.argtypes = [vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
+    L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
+                                                 ctypes.POINTER(u32)]  # diagnostic
+    L.myyuv_debug_k2_constants.argtypes = [ctypes.POINTER(u32)]  # diagnostic
     _lib = L
     return L
 
@@ -123,6 +126,18 @@ def strerror(code):
 
 def payload_bound(w, h):
     return load().myyuv_dct_payload_bound(w, h)
+
+
+def k2_constants():
+    """Diagnostic (not in include/myyuv_hip.h): the constants K2's overflow
+    regimes switch on, as the library was built (codec_common.hpp)."""
+    v = (ctypes.c_uint32 * 7)()
+    rc = load().myyuv_debug_k2_constants(v)
+    if rc:
+        raise CodecError(rc)
+    names = ("r16_gate_single", "r16_gate", "wave_encode_limit", "batch_wave_limit", "k2_group", "window_blocks",
+             "ovf_nub")
+    return dict(zip(names, (int(x) for x in v)))
 
 
 def batch_tiles(w, h):
@@ -417,3 +432,24 @@ class Codec:
         if rc:
             raise CodecError(rc)
         return [chunks[i, : sizes[i]].tobytes() for i in range(n)]
+
+    def huff_encode_blocks_counted(self, coef_zz, nframes=1):
+        """Diagnostic (not in include/myyuv_hip.h): huff_encode_blocks over a
+        batch of `nframes` frames (coef_zz: nframes x blocks-per-frame blocks),
+        as arrays: (chunks uint8[n, 160] zero-padded, sizes uint8[n], (the
+        length of K2's overflow list, of what the CAP-16 tier listed again, the
+        overflow passes' and the dense runs' chunk bytes as the tiles' info
+        words book them))."""
+        c = np.ascontiguousarray(coef_zz, np.int16).reshape(-1, 64)
+        n = c.shape[0]
+        if nframes < 1 or n % nframes:
+            raise ValueError("the block count is not a multiple of nframes")
+        chunks = np.zeros((n, 160), np.uint8)
+        sizes = np.zeros(n, np.uint8)
+        counts = (ctypes.c_uint32 * 4)()
+        rc = load().myyuv_debug_huff_encode_blocks(
+            self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), n // nframes, nframes, _u8(chunks),
+            _u8(sizes), counts)
+        if rc:
+            raise CodecError(rc)
+        return chunks, sizes, tuple(int(x) for x in counts)
