@@ -151,6 +151,64 @@ int myyuv_gpu_bmp_to_iyuv(myyuv_hip_handle h, const uint8_t* bmp_data, int32_t w
 int myyuv_gpu_bmp_to_iyuv_device(myyuv_hip_handle h, const void* d_bmp_data, int32_t width,
                                  int32_t height, uint16_t bit_count, void* d_iyuv, void* stream);
 
+/* IYUV -> BMP: the inverse of the above, and the headless form of what the
+ * reference's viewers do when they draw a frame (myyuv_opengl/viewer/
+ * frag_yuv.glsl over GL_LINEAR, clamp-to-edge plane textures,
+ * myyuv_opengl_shared.cpp:109-121; myyuv_sdl3/main.cpp:39-50).  No reference
+ * program emits these bytes, so the definition is stated here: the shader's
+ * arithmetic in fp32, left to right, no FMA contraction, then the UNORM8
+ * framebuffer write.  For luma pixel (x, y) of a WxH frame, rows top-down,
+ * Wc = W/2, Hc = H/2:
+ *   chroma NEAREST: su = 16 * U[y>>1][x>>1]; sv likewise.
+ *   chroma LINEAR (GL_LINEAR + CLAMP_TO_EDGE at 1:1):
+ *     cx = x>>1, nx = clamp(x odd ? cx+1 : cx-1, 0, Wc-1); cy, ny likewise in
+ *     y, clamped to [0, Hc-1];
+ *     su = 9*U[cy][cx] + 3*U[cy][nx] + 3*U[ny][cx] + U[ny][nx]  (0..4080); sv
+ *     likewise.  The clamp is per frame: in a batch a neighbour never comes
+ *     from another frame or plane.
+ *   yf = (float)Y / 255.0f
+ *   uf = (float)su / 4080.0f - 0.5f;  vf = (float)sv / 4080.0f - 0.5f
+ *   r = yf + 1.403f*vf;  g = (yf - 0.714f*vf) - 0.344f*uf;  b = yf + 1.773f*uf
+ *   byte = (uint8_t)floorf(fminf(fmaxf(c, 0.0f), 1.0f) * 255.0f + 0.5f)
+ * Faithful to the shader, mid-grey is not neutral: (Y, U, V) = (128, 128, 128)
+ * gives (B, G, R) = (129, 127, 129).  Under LINEAR green depends on the order
+ * of the two subtractions and on their products not being fused; the kernel
+ * keeps both.
+ * Output: the pixel array of a BMP whose header carries `width` / `height`
+ * (signed, the conventions and checks of myyuv_gpu_bmp_to_iyuv: the inverse
+ * of BMP::colorData, myyuv_bmp.cpp:80-103, so feeding the result back with
+ * the same signs sees the pixels top-down); B, G, R per pixel for bit_count
+ * 24 and B, G, R, 0xFF for 32; |width|*|height|*bit_count/8 bytes.  `iyuv`
+ * is |width|*|height|*3/2 bytes.  Errors: MYYUV_E_BMP_INVALID (|width| % 4,
+ * bit_count 0: BMP::isValidHeader must accept the result), MYYUV_E_BMP_SIGN,
+ * MYYUV_E_BMP_UNSUPPORTED (odd height, not 24/32 bpp), MYYUV_E_ARG (a chroma
+ * mode other than the two below; more than 4 GiB of BGRA). */
+#define MYYUV_CHROMA_NEAREST 0
+#define MYYUV_CHROMA_LINEAR 1
+int myyuv_gpu_iyuv_to_bmp(myyuv_hip_handle h, const uint8_t* iyuv, int32_t width, int32_t height,
+                          uint16_t bit_count, uint32_t chroma, uint8_t* bmp_data);
+/* Device-resident variant for `nframes` frames of one geometry (frame f at
+ * d_iyuv + f*W*H*3/2 -> d_bmp_data + f*W*H*bit_count/8), asynchronous on
+ * `stream` (NULL = the context's), no allocation; argument errors are
+ * returned at once.  d_iyuv is 4-byte aligned, d_bmp_data 16-byte (32 bpp) or
+ * 4-byte (24 bpp) aligned: a misaligned pointer, like nframes == 0, is
+ * MYYUV_E_ARG (after the errors listed above).
+ * These two calls check every other argument before the handle (a null
+ * handle is MYYUV_E_ARG last), so the argument errors can be had without a
+ * device; the two decompress_to_bmp calls below check the handle first, as
+ * the decompress calls do. */
+int myyuv_gpu_iyuv_to_bmp_device(myyuv_hip_handle h, const void* d_iyuv, uint32_t nframes, int32_t width,
+                                 int32_t height, uint16_t bit_count, uint32_t chroma, void* d_bmp_data,
+                                 void* stream);
+/* Decode and convert, the IYUV frame staying in HBM: myyuv_gpu_dct_decompress
+ * (same stream checks, errors and *bad_block, in the same order) followed by
+ * myyuv_gpu_iyuv_to_bmp (its argument errors come after the stream header's
+ * and before the % 8 dimension checks, which |width| and |height| must pass
+ * too). */
+int myyuv_gpu_dct_decompress_to_bmp(myyuv_hip_handle h, const uint8_t* payload, uint32_t size, int32_t width,
+                                    int32_t height, const uint8_t quality[3], uint16_t bit_count,
+                                    uint32_t chroma, uint8_t* bmp_data, int64_t* bad_block);
+
 /* Host-buffer batches (many frames per call; §7 step 9:
  * transfers overlapped with the kernels).  The batch runs in chunks of up to
  * 8 frames through two device slots: chunk k's host -> device copies, chunk
@@ -186,6 +244,14 @@ int myyuv_gpu_dct_decompress_frames(myyuv_hip_handle h, const uint8_t* const* pa
 int myyuv_gpu_dct_decompress_batch(myyuv_hip_handle h, const uint8_t* payloads, const uint32_t* sizes,
                                    uint32_t cap, uint32_t nframes, uint32_t width, uint32_t height,
                                    const uint8_t quality[3], uint8_t* iyuv, int64_t* bad_block);
+/* myyuv_gpu_dct_decompress_frames with each frame converted on the device
+ * (myyuv_gpu_dct_decompress_to_bmp's conversion): stream f -> bmps[f]
+ * (|width|*|height|*bit_count/8 bytes).  Header checks, error order and
+ * *bad_block as myyuv_gpu_dct_decompress_frames. */
+int myyuv_gpu_dct_decompress_to_bmp_frames(myyuv_hip_handle h, const uint8_t* const* payloads,
+                                           const uint32_t* sizes, uint32_t nframes, int32_t width,
+                                           int32_t height, const uint8_t quality[3], uint16_t bit_count,
+                                           uint32_t chroma, uint8_t* const* bmps, int64_t* bad_block);
 
 /* Waits for `stream`, returns (and clears) the first device-side error since
  * the last call; *bad_block as above. */
@@ -208,7 +274,8 @@ int myyuv_hip_sync_status(myyuv_hip_handle h, void* stream, int64_t* bad_block);
 #define MYYUV_K_HUFF_WAVE 9  /* K2 overflow pass, wave per block (short worklists) */
 #define MYYUV_K_BMP 10       /* K7 bmp_to_iyuv (BMP -> IYUV conversion) */
 #define MYYUV_K_FDCT_FIX 11  /* K1's exact path for the units K1 listed (fdct_fix) */
-#define MYYUV_K_COUNT 12
+#define MYYUV_K_IYUV_BMP 12  /* K8 iyuv_to_bmp (IYUV -> BMP conversion) */
+#define MYYUV_K_COUNT 13
 int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 /* As myyuv_hip_profile, but stamps only the kernels whose bit (1 << MYYUV_K_*)
  * is set in `mask` (0 disables): event stamping costs host and queue time per

@@ -9,6 +9,9 @@
 // (main.cpp:100-136):
 //   myyuv_cli in.bmp -info
 //   myyuv_cli in.bmp -to_yuv IYUV -o out.myyuv   (conversion on the GPU, K7)
+// the way back, which the reference leaves to its viewers (K8; a compressed
+// input is decoded and converted on the device):
+//   myyuv_cli in.myyuv -to_bmp [24|32] [-chroma nearest|linear] -o out.bmp
 // and, beyond the reference CLI, many frames per invocation (SURVEY.md §8f
 // row 2; frames of one geometry share batched kernel launches):
 //   myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IN.myyuv...
@@ -42,6 +45,7 @@ void usage() {
             << "  myyuv_cli IMAGE.myyuv -info\n"
             << "  myyuv_cli IMAGE.myyuv -compress DCT Q [Q [Q]] -o OUT.myyuv   (Q in 1..100, per plane Y U V)\n"
             << "  myyuv_cli IMAGE.myyuv -decompress -o OUT.myyuv\n"
+            << "  myyuv_cli IMAGE.myyuv -to_bmp [24|32] [-chroma nearest|linear] -o OUT.bmp\n"
             << "  myyuv_cli IMAGE.bmp -info\n"
             << "  myyuv_cli IMAGE.bmp -to_yuv IYUV -o OUT.myyuv\n"
             << "  myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IMAGE.myyuv...\n"
@@ -123,6 +127,40 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     myyuv::YUV out;
     const float ms = elapsed_ms([&] { out = yuv.decompress(); });
     std::cout << "YUV DCT decompression : " << ms << " ms\n";
+    out.dump(args[a + 1]);
+    return 0;
+  }
+  if (cmd == "-to_bmp") {  // [24|32] [-chroma nearest|linear] -o OUT.bmp; the viewer's defaults
+    a++;
+    uint16_t bits = 32;
+    uint32_t chroma = 1;  // MYYUV_CHROMA_LINEAR
+    std::string mode = "linear";
+    if (a < args.size() && args[a] != "-o" && args[a] != "-chroma") {
+      if (args[a] != "24" && args[a] != "32") {
+        std::cout << "Invalid bit count " << args[a] << ", must be 24 or 32\n";
+        usage();
+        return 1;
+      }
+      bits = (uint16_t)std::stoi(args[a++]);
+    }
+    if (a < args.size() && args[a] == "-chroma") {
+      if (a + 1 >= args.size() || (args[a + 1] != "nearest" && args[a + 1] != "linear")) {
+        std::cout << "Invalid argument, -chroma must be followed by `nearest` or `linear`\n";
+        usage();
+        return 1;
+      }
+      mode = args[a + 1];
+      chroma = mode == "linear" ? 1 : 0;
+      a += 2;
+    }
+    if (args.size() != a + 2 || args[a] != "-o") {
+      std::cout << "Invalid argument, last arguments must be `-o /path/to/new_image.bmp`\n";
+      usage();
+      return 1;
+    }
+    myyuv::BMP out;
+    const float ms = elapsed_ms([&] { out = myyuv::yuv_to_bmp(yuv, bits, chroma); });
+    std::cout << "YUV to BMP (" << bits << " " << mode << ") : " << ms << " ms\n";
     out.dump(args[a + 1]);
     return 0;
   }

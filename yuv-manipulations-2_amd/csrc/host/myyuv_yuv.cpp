@@ -295,6 +295,46 @@ void YUV::dump(const std::string& path) const {
   f.write(reinterpret_cast<const char*>(data), header.data_size);
 }
 
+BMP yuv_to_bmp(const YUV& yuv, uint16_t bit_count, uint32_t chroma) {
+  static_assert(MYYUV_CHROMA_LINEAR == 1, "the header's default chroma mode");
+  if (!yuv.isValid()) throw std::runtime_error("YUV is invalid");
+  if (yuv.getFourccFormat() != YUV::FourccFormats::IYUV) throw std::runtime_error("Incorrect format");
+  if (bit_count != 24 && bit_count != 32) fail(MYYUV_E_BMP_UNSUPPORTED);
+  const uint32_t w = yuv.header.width, h = yuv.header.height;
+  // BMP::imageSize(), file_size and dump() hold the pixel array's size in 32
+  // bits, and imageSize() forms w * h * bit_count before it divides: an image
+  // past that cannot be a BMP (and a wrapped size would under-allocate `data`)
+  const uint64_t bytes = (uint64_t)w * h * (bit_count / 8);
+  if ((uint64_t)w * h * bit_count > 0xFFFFFFFFull || w > 0x7FFFFFFFu || h > 0x7FFFFFFFu) fail(MYYUV_E_ARG);
+  BMP res;
+  BMPHeader& bh = res.header;
+  bh.width = (int32_t)w;  // bottom-up rows
+  bh.height = (int32_t)h;
+  bh.planes = 1;
+  bh.bit_count = bit_count;
+  bh.header_size = bit_count == 32 ? 124 : 40;
+  bh.compression = bit_count == 32 ? 3 : 0;
+  bh.data_pos = (uint32_t)(sizeof(BMPHeader) + (bit_count == 32 ? sizeof(BMPColorHeader) : 0));
+  if (res.imageSize() != bytes || bytes > 0xFFFFFFFFull - bh.data_pos) fail(MYYUV_E_ARG);
+  bh.file_size = bh.data_pos + (uint32_t)bytes;
+  res.data = new uint8_t[bytes ? bytes : 1];
+  int rc;
+  if (yuv.getCompression() == YUV::Compressions::NONE) {
+    if (yuv.header.data_size < (uint64_t)w * h * 3 / 2) throw std::runtime_error("YUV is invalid");
+    rc = myyuv_gpu_iyuv_to_bmp(t_codec.get(), yuv.data, bh.width, bh.height, bit_count, chroma, res.data);
+  } else if (yuv.getCompression() == YUV::Compressions::DCT) {
+    if (yuv.header.compression_params_size != 3)
+      throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
+    int64_t bad = -1;
+    rc = myyuv_gpu_dct_decompress_to_bmp(t_codec.get(), yuv.data, yuv.header.data_size, bh.width, bh.height,
+                                         yuv.compression_params, bit_count, chroma, res.data, &bad);
+  } else {
+    throw std::runtime_error("Error this decompression is unimplemented");
+  }
+  if (rc) fail(rc);
+  return res;
+}
+
 }  // namespace myyuv
 
 namespace myyuvDCT {

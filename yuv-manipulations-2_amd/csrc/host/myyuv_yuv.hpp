@@ -100,6 +100,14 @@ class YUV {
   void dump(const std::string& path) const;
 };
 
+// IYUV -> BMP on the GPU (K8; the conversion the reference's viewers draw
+// with, defined in include/myyuv_hip.h): a bottom-up BMP (width, height > 0)
+// of bit_count 24 or 32 with the headers BMP::dump writes.  chroma: 0 nearest
+// sample, 1 bilinear (MYYUV_CHROMA_NEAREST / MYYUV_CHROMA_LINEAR).  An
+// uncompressed frame goes through myyuv_gpu_iyuv_to_bmp, a DCT-compressed one
+// through myyuv_gpu_dct_decompress_to_bmp (decoded and converted on the device).
+BMP yuv_to_bmp(const YUV& yuv, uint16_t bit_count = 32, uint32_t chroma = 1 /* MYYUV_CHROMA_LINEAR */);
+
 }  // namespace myyuv
 
 namespace myyuvDCT {

@@ -53,6 +53,8 @@ __global__ void k_huff_decode(const uint8_t*, const uint32_t*, uint32_t, const S
                               uint4*, uint8_t*, unsigned long long*);
 template <int BPP>
 __global__ void k_bmp_to_iyuv(const uint8_t*, uint32_t, uint32_t, uint32_t, uint8_t*);
+template <int BPP, int LINEAR>
+__global__ void k_iyuv_to_bmp(const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t*);
 }  // namespace myyuv_gpu
 
 using namespace myyuv_gpu;
@@ -132,7 +134,8 @@ struct myyuv_hip_ctx {
   hipStream_t last_stream = nullptr;
   DevBuf frame, coef, sizes, loff, tiles, payload, err, psize, desc, work, qtd;
   DevBuf stage, oslots, tinfo, srcoff;  // K2 -> K4 (codec_common.hpp)
-  DevBuf bmp;   // staged BMP pixels (host-buffer BMP -> IYUV)
+  DevBuf bmp;   // staged BMP pixels (host-buffer BMP -> IYUV and back)
+  DevBuf dframes;  // a chunk's decoded IYUV frames between the decoder and K8 (decompress_to_bmp_frames)
   DevBuf rmask; // per block: bit c = coefficient row c nonzero (K1 -> overflow passes, K5 -> K6)
   DevBuf binfo; // per block: K1 -> K2's classification (binfo_word, codec_common.hpp)
   DevBuf zq;    // 256 zero bytes: K6's source for rows the mask says are zero

@@ -1,4 +1,7 @@
-// k_color.hip — K7: BMP (BGR / BGRA) -> IYUV 4:2:0, the step before compress
+// k_color.hip — the colour conversions at the two ends of the pixel path:
+// K7 BMP -> IYUV (below) and K8 IYUV -> BMP (further down).
+//
+// K7: BMP (BGR / BGRA) -> IYUV 4:2:0, the step before compress
 // (SURVEY.md §8f row 3).  Replaces YUV(const BMP&, IYUV): bmp_to_yuv_map[IYUV]
 // (myyuv_lib/myyuv_yuv.cpp:88-128) over BMP::colorData (myyuv_bmp.cpp:77-101),
 // getYUV444FromRGB2x2 (myyuv_yuv.cpp:34-52) and divide_roundnearest<uint8_t>
@@ -24,6 +27,7 @@
 #include <cstdint>
 
 #include "codec_common.hpp"
+#include "color_div.hpp"
 
 namespace myyuv_gpu {
 
@@ -117,5 +121,182 @@ __global__ __launch_bounds__(256) void k_bmp_to_iyuv(const uint8_t* __restrict__
 
 template __global__ void k_bmp_to_iyuv<3>(const uint8_t*, uint32_t, uint32_t, uint32_t, uint8_t*);
 template __global__ void k_bmp_to_iyuv<4>(const uint8_t*, uint32_t, uint32_t, uint32_t, uint8_t*);
+
+// ---- K8: IYUV -> BMP (BGR / BGRA), the inverse of K7 ------------------------
+//
+// The conversion the reference's viewers perform when they draw a frame
+// (myyuv_opengl/viewer/frag_yuv.glsl over the plane textures of
+// myyuv_opengl_shared.cpp:109-121), as a BMP pixel array.  Defined bit for
+// bit in include/myyuv_hip.h (myyuv_gpu_iyuv_to_bmp): fp32, left to right, no
+// FMA contraction, then the UNORM8 write floor(clamp(c, 0, 1) * 255 + 0.5).
+//
+// Pure streaming, 1.5 B read + 3 or 4 B written per pixel; the stores
+// dominate.  K7's shape: a lane converts a 4x2 tile and writes one 16-B
+// (BGRA) or 12-B (BGR) store per tile row, consecutive lanes on consecutive
+// tiles of one tile row (1 KiB per wave-instruction).  A workgroup is four
+// waves on four tile rows (block 64 x 4) and walks tile rows (y) and frames
+// (z), so a wave's row addressing is uniform and no lane divides.  The re-orientation is folded into the
+// destination addressing.
+//
+// LINEAR chroma needs, per plane, columns 2tx-1 .. 2tx+2 of chroma rows
+// ty-1 .. ty+1: one dword load per row from the (unaligned) byte 2tx-1.  At
+// the frame's left / right edge the load starts inside the row (column 0 /
+// Wc-4) and the window is shifted in the register with the edge sample
+// repeated; rows clamp to the frame's own plane, so no byte outside a row is
+// read and a batch's neighbours never come from another frame.
+//
+// The two true divisions (Y / 255, s / 4080) are two operations each
+// (div255 / div4080, color_div.hpp: correctly rounded for every numerator
+// that occurs, which tests/test_yuv_to_bmp_host.py checks on the host).
+namespace {
+
+// the framebuffer write: UNORM8 of a colour component (the cast truncates,
+// which is the definition's floor: the sum is in [0.5, 255.5])
+__device__ __forceinline__ uint32_t unorm8(float c) {
+  return (uint32_t)(fminf(fmaxf(c, 0.0f), 1.0f) * 255.0f + 0.5f);
+}
+
+// A chroma pair's contributions to r, g, g, b from the sample sums (16 x the
+// sample for NEAREST, the 9/3/3/1 sum for LINEAR: both over 4080).
+struct Chroma {
+  float rv, gv, gu, bu;
+};
+__device__ __forceinline__ Chroma chroma(uint32_t su, uint32_t sv) {
+  const float uf = div4080((float)su) - 0.5f;
+  const float vf = div4080((float)sv) - 0.5f;
+  return {1.403f * vf, 0.714f * vf, 0.344f * uf, 1.773f * uf};
+}
+
+// B | G << 8 | R << 16 of one pixel
+__device__ __forceinline__ uint32_t bgr(uint32_t y, const Chroma& c) {
+  const float yf = div255((float)y);
+  const float r = yf + c.rv;
+  const float g = (yf - c.gv) - c.gu;
+  const float b = yf + c.bu;
+  return unorm8(b) | unorm8(g) << 8 | unorm8(r) << 16;
+}
+
+__device__ __forceinline__ uint32_t load32(const uint8_t* p) {  // any alignment
+  uint32_t v;
+  __builtin_memcpy(&v, p, 4);
+  return v;
+}
+
+// Columns 2tx-1 .. 2tx+2 of a chroma row (one per byte, low byte first), the
+// row's edge samples repeated past its ends (CLAMP_TO_EDGE).  wc >= 2, even.
+__device__ __forceinline__ uint32_t window4(const uint8_t* __restrict__ row, uint32_t tx, uint32_t tiles_x,
+                                            uint32_t wc) {
+  if (wc == 2) {  // (uniform) one tile per row: c0 c0 c1 c1
+    const uint32_t v = *reinterpret_cast<const uint16_t*>(row);
+    return (v & 0xFFu) * 0x0101u | (v >> 8) * 0x01010000u;
+  }
+  const uint32_t s = tx == 0 ? 0u : (tx == tiles_x - 1 ? wc - 4 : 2 * tx - 1);
+  const uint32_t v = load32(row + s);
+  if (tx == 0) return v << 8 | (v & 0xFFu);                   // c0 c0 c1 c2
+  if (tx == tiles_x - 1) return v >> 8 | (v & 0xFF000000u);  // c[wc-3] c[wc-2] c[wc-1] c[wc-1]
+  return v;
+}
+
+// 3 * sample + neighbour along x for the tile's four luma columns: column k
+// samples window byte 1 + k / 2, its neighbour is byte k / 2 + 2 * (k & 1)
+// (left for even x, right for odd x).
+__device__ __forceinline__ void hsum(uint32_t w, uint32_t (&h)[4]) {
+  const uint32_t b0 = w & 0xFFu, b1 = (w >> 8) & 0xFFu, b2 = (w >> 16) & 0xFFu, b3 = w >> 24;
+  h[0] = 3 * b1 + b0;
+  h[1] = 3 * b1 + b2;
+  h[2] = 3 * b2 + b1;
+  h[3] = 3 * b2 + b3;
+}
+
+template <int BPP>
+__device__ __forceinline__ void store4(uint8_t* __restrict__ dst, size_t pix, const uint32_t (&p)[4]) {
+  uint32_t* q = reinterpret_cast<uint32_t*>(dst + pix * BPP);
+  if constexpr (BPP == 4) {
+    *reinterpret_cast<uint4*>(q) =
+        make_uint4(p[0] | 0xFF000000u, p[1] | 0xFF000000u, p[2] | 0xFF000000u, p[3] | 0xFF000000u);
+  } else {
+    q[0] = p[0] | p[1] << 24;
+    q[1] = p[1] >> 8 | p[2] << 16;
+    q[2] = p[2] >> 16 | p[3] << 8;
+  }
+}
+
+}  // namespace
+
+// Block (64, 4); grid (ceil(W / 4 / 64), tile rows / 4, frames), the last two strided.  Frame f
+// at src + f * W * H * 3 / 2 -> dst + f * W * H * BPP.  orient as K7's, for
+// the destination.  LINEAR: 0 = nearest chroma sample, 1 = the bilinear
+// 9/3/3/1 weights of GL_LINEAR at 1:1.
+template <int BPP, int LINEAR>
+__global__ __launch_bounds__(256) void k_iyuv_to_bmp(const uint8_t* __restrict__ src, uint32_t W, uint32_t H,
+                                                     uint32_t nframes, uint32_t orient,
+                                                     uint8_t* __restrict__ dst) {
+  const uint32_t tiles_x = W / 4, tiles_y = H / 2, wc = W / 2, hc = H / 2;
+  const size_t npx = (size_t)W * H;
+  const uint32_t tx = blockIdx.x * 64 + threadIdx.x;
+  if (tx >= tiles_x) return;
+  const uint32_t c = 4 * tx;
+  for (uint32_t f = blockIdx.z; f < nframes; f += gridDim.z) {
+    const uint8_t* __restrict__ yp = src + (size_t)f * (npx / 2 * 3);
+    const uint8_t* __restrict__ up = yp + npx;
+    const uint8_t* __restrict__ vp = up + npx / 4;
+    uint8_t* __restrict__ out = dst + (size_t)f * npx * BPP;
+    for (uint32_t ty = blockIdx.y * 4 + threadIdx.y; ty < tiles_y; ty += gridDim.y * 4) {
+      const uint32_t r = 2 * ty;
+      const uint32_t Y[2] = {*reinterpret_cast<const uint32_t*>(yp + (size_t)r * W + c),
+                             *reinterpret_cast<const uint32_t*>(yp + (size_t)(r + 1) * W + c)};
+      // chroma sums of the tile's 2 x 4 pixels
+      uint32_t su[2][4], sv[2][4];
+      if constexpr (LINEAR) {
+        // rows ty-1, ty, ty+1 of this frame's plane: the even luma row's
+        // neighbour is the row above, the odd one's the row below
+        const size_t rows[3] = {(size_t)(ty == 0 ? 0 : ty - 1) * wc, (size_t)ty * wc,
+                                (size_t)(ty + 1 == hc ? ty : ty + 1) * wc};
+        uint32_t hu[3][4], hv[3][4];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+          hsum(window4(up + rows[i], tx, tiles_x, wc), hu[i]);
+          hsum(window4(vp + rows[i], tx, tiles_x, wc), hv[i]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          su[0][k] = 3 * hu[1][k] + hu[0][k], su[1][k] = 3 * hu[1][k] + hu[2][k];
+          sv[0][k] = 3 * hv[1][k] + hv[0][k], sv[1][k] = 3 * hv[1][k] + hv[2][k];
+        }
+      } else {
+        const uint32_t u2 = *reinterpret_cast<const uint16_t*>(up + (size_t)ty * wc + 2 * tx);
+        const uint32_t v2 = *reinterpret_cast<const uint16_t*>(vp + (size_t)ty * wc + 2 * tx);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          su[0][k] = su[1][k] = 16 * ((u2 >> (8 * (k >> 1))) & 0xFFu);
+          sv[0][k] = sv[1][k] = 16 * ((v2 >> (8 * (k >> 1))) & 0xFFu);
+        }
+      }
+#pragma unroll
+      for (int dr = 0; dr < 2; dr++) {
+        uint32_t p[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          // NEAREST: a 2x2 quad shares its chroma terms (the compiler merges the equal expressions)
+          p[k] = bgr((Y[dr] >> (8 * k)) & 0xFFu, chroma(su[dr][k], sv[dr][k]));
+        }
+        const size_t lin = (size_t)(r + dr) * W + c;  // top-down pixel index of the tile row
+        if (orient == 0) {
+          store4<BPP>(out, lin, p);
+        } else if (orient == 1) {  // pixels lin .. lin+3 go to npx-1-lin .. npx-4-lin
+          const uint32_t q[4] = {p[3], p[2], p[1], p[0]};
+          store4<BPP>(out, npx - 4 - lin, q);
+        } else {
+          store4<BPP>(out, (size_t)(H - 1 - (r + dr)) * W + c, p);
+        }
+      }
+    }
+  }
+}
+
+template __global__ void k_iyuv_to_bmp<3, 0>(const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t*);
+template __global__ void k_iyuv_to_bmp<3, 1>(const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t*);
+template __global__ void k_iyuv_to_bmp<4, 0>(const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t*);
+template __global__ void k_iyuv_to_bmp<4, 1>(const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t*);
 
 }  // namespace myyuv_gpu

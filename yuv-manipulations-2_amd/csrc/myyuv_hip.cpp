@@ -709,6 +709,62 @@ int myyuv_gpu_bmp_to_iyuv(myyuv_hip_handle c, const uint8_t* bmp_data, int32_t w
   return 0;
 }
 
+// ---- K8: IYUV -> BMP (the viewers' conversion; defined in myyuv_hip.h) ----
+namespace {
+
+// nf frames (frame f at src + f * W*H*3/2 -> dst + f * W*H*bits/8).  Four tile
+// rows per workgroup, at most about 8192 workgroups striding over tile rows
+// and frames.
+int launch_to_bmp(myyuv_hip_ctx* c, const void* src, uint32_t W, uint32_t H, uint32_t nf, uint32_t orient,
+                  uint16_t bits, uint32_t chroma, void* dst, hipStream_t s) {
+  if (W == 0 || H == 0 || nf == 0) return 0;
+  const uint32_t gx = ceil_div(W / 4, 64);
+  const uint32_t gy = std::min(ceil_div(H / 2, 4), std::max(1u, 8192u / gx));
+  const uint32_t gz = std::min(nf, std::max(1u, 8192u / (gx * gy)));
+  const uint8_t* in = static_cast<const uint8_t*>(src);
+  uint8_t* out = static_cast<uint8_t*>(dst);
+  const dim3 grid(gx, gy, gz), block(64, 4);
+  auto* k = bits == 32 ? (chroma ? k_iyuv_to_bmp<4, 1> : k_iyuv_to_bmp<4, 0>)
+                       : (chroma ? k_iyuv_to_bmp<3, 1> : k_iyuv_to_bmp<3, 0>);
+  return launch(c, MYYUV_K_IYUV_BMP, k, grid, block, s, in, W, H, nf, orient, out);
+}
+
+bool chroma_ok(uint32_t chroma) { return chroma == MYYUV_CHROMA_NEAREST || chroma == MYYUV_CHROMA_LINEAR; }
+
+}  // namespace
+
+int myyuv_gpu_iyuv_to_bmp_device(myyuv_hip_handle c, const void* d_iyuv, uint32_t nframes, int32_t width,
+                                 int32_t height, uint16_t bit_count, uint32_t chroma, void* d_bmp, void* stream) {
+  if (!d_iyuv || !d_bmp || nframes == 0 || !chroma_ok(chroma)) return MYYUV_E_ARG;
+  uint32_t W = 0, H = 0, orient = 0;
+  int e = bmp_check(width, height, bit_count, &W, &H, &orient);
+  if (e) return e;
+  // the kernel's dword luma loads and its 16-B / dword stores
+  if (((uintptr_t)d_iyuv & 3) || ((uintptr_t)d_bmp & (bit_count == 32 ? 15 : 3))) return MYYUV_E_ARG;
+  if (!c) return MYYUV_E_ARG;  // (last: the argument checks above need no context)
+  Entry en(c, stream);
+  return launch_to_bmp(c, d_iyuv, W, H, nframes, orient, bit_count, chroma, d_bmp, en.s);
+}
+
+int myyuv_gpu_iyuv_to_bmp(myyuv_hip_handle c, const uint8_t* iyuv, int32_t width, int32_t height,
+                          uint16_t bit_count, uint32_t chroma, uint8_t* bmp_data) {
+  if (!iyuv || !bmp_data || !chroma_ok(chroma)) return MYYUV_E_ARG;
+  uint32_t W = 0, H = 0, orient = 0;
+  int e = bmp_check(width, height, bit_count, &W, &H, &orient);
+  if (e) return e;
+  if (!c) return MYYUV_E_ARG;  // (last: the argument checks above need no context)
+  Entry en(c);
+  hipStream_t s = en.s;
+  const size_t in_bytes = (size_t)W * H * 3 / 2, out_bytes = (size_t)W * H * (bit_count / 8);
+  if (in_bytes == 0) return 0;
+  if (c->frame.grow(in_bytes) || c->bmp.grow(out_bytes)) return MYYUV_E_HIP;
+  if (h2d(c->frame.p, iyuv, in_bytes, s)) return MYYUV_E_HIP;
+  if ((e = launch_to_bmp(c, c->frame.p, W, H, 1, orient, bit_count, chroma, c->bmp.p, s))) return e;
+  if (d2h(bmp_data, c->bmp.p, out_bytes, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
 int myyuv_hip_sync_status(myyuv_hip_handle c, void* stream, int64_t* bad_block) {
   if (!c) return MYYUV_E_ARG;
   Entry en(c, stream);
@@ -786,6 +842,44 @@ int myyuv_gpu_dct_decompress(myyuv_hip_handle c, const uint8_t* payload, uint32_
   return 0;
 }
 
+// myyuv_gpu_dct_decompress with K8 behind the decoder: the frame goes from
+// the decoder to the conversion in the context's `frame` buffer.
+int myyuv_gpu_dct_decompress_to_bmp(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, int32_t width,
+                                    int32_t height, const uint8_t q[3], uint16_t bit_count, uint32_t chroma,
+                                    uint8_t* bmp_data, int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payload || !bmp_data || !q || !chroma_ok(chroma)) return MYYUV_E_ARG;
+  int e = check_q(q);
+  if (e) return e;
+  FrameGeom G;
+  uint32_t w = 0, h = 0, orient = 0;
+  if ((e = host_parse_headers(payload, size)) || (e = bmp_check(width, height, bit_count, &w, &h, &orient)) ||
+      (e = make_geom(w, h, G)))
+    return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const uint32_t cap = (size + 3) & ~3u;
+  const size_t fbytes = (size_t)w * h * 3 / 2, out_bytes = (size_t)w * h * (bit_count / 8);
+  if ((e = reserve(c, G)) || (e = set_qtables(c, q, s))) return e;
+  if (c->frame.grow(fbytes) || c->payload.grow(cap) || c->bmp.grow(out_bytes)) return MYYUV_E_HIP;
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (hipMemsetAsync(static_cast<uint8_t*>(c->payload.p) + (cap - 4), 0, 4, s) != hipSuccess ||
+      h2d(c->payload.p, payload, size, s) ||
+      hipMemcpyAsync(c->psize.p, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  if ((e = launch_decompress(c, G, c->payload.p, c->psize.as<const uint32_t>(), cap, c->frame.p, s)) ||
+      (e = launch_to_bmp(c, c->frame.p, w, h, 1, orient, bit_count, chroma, c->bmp.p, s)))
+    return e;
+  if ((e = read_err(c, s, bad_block))) {
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  if (d2h(bmp_data, c->bmp.p, out_bytes, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
 // ---- host-buffer batches, pipelined ------------------
 //
 // The batch is cut into chunks of B frames, alternating between two device
@@ -851,14 +945,17 @@ struct PipeDrain {
 };
 
 // The pipeline of both directions (tag: 'c' / 'd' in the trace).  A frame
-// takes in_slot / out_slot bytes of a slot's input / output buffer.  The
+// takes in_slot / out_slot bytes of a slot's input / output buffer, and
+// mid_slot bytes (0: none) of c->dframes, a chunk's scratch between two of
+// its kernels.  The
 // direction's own steps, each for the n frames from f0 on in slot sl:
 //   upload(P, sl, f0, n)       queues the chunk's host -> device copies on P.cin
 //   run(P, GK, sl, perr, s)    launches its kernels on s (error word: perr)
 //   download(P, sl, f0, n)     once they are done: queues the device -> host copies on P.cout
 extern "C++" template <class Upload, class Run, class Download>
 int pipe_frames(myyuv_hip_ctx* c, char tag, uint32_t nf, uint32_t w, uint32_t h, const uint8_t q[3],
-                size_t in_slot, size_t out_slot, int64_t* bad_block, Upload upload, Run run, Download download) {
+                size_t in_slot, size_t out_slot, size_t mid_slot, int64_t* bad_block, Upload upload, Run run,
+                Download download) {
   FrameGeom G;
   int e = make_geom(w, h, G);
   if (e) return e;
@@ -871,6 +968,7 @@ int pipe_frames(myyuv_hip_ctx* c, char tag, uint32_t nf, uint32_t w, uint32_t h,
   HostPipe& P = *c->pipe;
   for (int k = 0; k < 2; k++)
     if (P.pin[k].grow(in_slot * B) || P.pout[k].grow(out_slot * B)) return MYYUV_E_HIP;
+  if (c->dframes.grow(mid_slot * B)) return MYYUV_E_HIP;  // (kernels run one chunk at a time: one slot)
   PipeDrain drain{c};
   const uint32_t nchunks = ceil_div(nf, B);
   // chunk k's sizes and error word are on the host: its results go back
@@ -919,7 +1017,7 @@ int compress_frames(myyuv_hip_ctx* c, const uint8_t* const* frames, uint32_t nf,
   const size_t fb = (size_t)w * h * 3 / 2;
   const uint32_t dcap = (myyuv_dct_payload_bound(w, h) + 3) & ~3u;  // device slot per frame
   return pipe_frames(
-      c, 'c', nf, w, h, q, fb, dcap, nullptr,
+      c, 'c', nf, w, h, q, fb, dcap, 0, nullptr,
       [&](HostPipe& P, uint32_t sl, uint32_t f0, uint32_t n) {
         int e = 0;
         for (uint32_t i = 0; i < n && !e; i++)
@@ -947,13 +1045,23 @@ int compress_frames(myyuv_hip_ctx* c, const uint8_t* const* frames, uint32_t nf,
       });
 }
 
+// K8 behind the decoder (decompress_to_bmp_frames): how the frames leave
+struct ToBmp {
+  uint32_t orient, chroma;
+  uint16_t bits;
+};
+
+// Streams -> frames[f]: the IYUV frame, or (bmp) its BMP pixel array, which
+// K8 writes into the output slot from the chunk's frames in c->dframes.
 int decompress_frames(myyuv_hip_ctx* c, const uint8_t* const* payloads, const uint32_t* psizes, uint32_t nf,
-                      uint32_t w, uint32_t h, const uint8_t q[3], uint8_t* const* frames, int64_t* bad_block) {
+                      uint32_t w, uint32_t h, const uint8_t q[3], uint8_t* const* frames, int64_t* bad_block,
+                      const ToBmp* bmp = nullptr) {
   const size_t fb = (size_t)w * h * 3 / 2;
+  const size_t ob = bmp ? (size_t)w * h * (bmp->bits / 8) : fb;  // output bytes per frame
   uint32_t icap = 4;  // device slot per stream: the longest, 4-aligned
   for (uint32_t f = 0; f < nf; f++) icap = std::max(icap, (psizes[f] + 3u) & ~3u);
   return pipe_frames(
-      c, 'd', nf, w, h, q, icap, fb, bad_block,
+      c, 'd', nf, w, h, q, icap, ob, bmp ? fb : 0, bad_block,
       [&](HostPipe& P, uint32_t sl, uint32_t f0, uint32_t n) {
         uint8_t* slot = P.pin[sl].as<uint8_t>();
         for (uint32_t i = 0; i < n; i++) {
@@ -966,11 +1074,15 @@ int decompress_frames(myyuv_hip_ctx* c, const uint8_t* const* payloads, const ui
         return h2d(P.psz[sl].p, psizes + f0, (size_t)n * 4, P.cin);
       },
       [&](HostPipe& P, const FrameGeom& GK, uint32_t sl, unsigned long long* perr, hipStream_t s) {
-        return launch_decompress(c, GK, P.pin[sl].p, P.psz[sl].as<const uint32_t>(), icap, P.pout[sl].p, s, perr);
+        if (!bmp)
+          return launch_decompress(c, GK, P.pin[sl].p, P.psz[sl].as<const uint32_t>(), icap, P.pout[sl].p, s, perr);
+        if (int e = launch_decompress(c, GK, P.pin[sl].p, P.psz[sl].as<const uint32_t>(), icap, c->dframes.p, s, perr))
+          return e;
+        return launch_to_bmp(c, c->dframes.p, w, h, GK.nframes, bmp->orient, bmp->bits, bmp->chroma, P.pout[sl].p, s);
       },
       [&](HostPipe& P, uint32_t sl, uint32_t f0, uint32_t n) {
         for (uint32_t i = 0; i < n; i++)
-          if (hipMemcpyAsync(frames[f0 + i], P.pout[sl].as<uint8_t>() + i * fb, fb, hipMemcpyDeviceToHost, P.cout) !=
+          if (hipMemcpyAsync(frames[f0 + i], P.pout[sl].as<uint8_t>() + i * ob, ob, hipMemcpyDeviceToHost, P.cout) !=
               hipSuccess)
             return MYYUV_E_HIP;
         return 0;
@@ -1040,6 +1152,23 @@ int myyuv_gpu_dct_decompress_batch(myyuv_hip_handle c, const uint8_t* payloads, 
     out[f] = iyuv + f * fb;
   }
   return myyuv_gpu_dct_decompress_frames(c, in.data(), sizes, nframes, w, h, q, out.data(), bad_block);
+}
+
+int myyuv_gpu_dct_decompress_to_bmp_frames(myyuv_hip_handle c, const uint8_t* const* payloads, const uint32_t* sizes,
+                                           uint32_t nframes, int32_t width, int32_t height, const uint8_t q[3],
+                                           uint16_t bit_count, uint32_t chroma, uint8_t* const* bmps,
+                                           int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payloads || !sizes || !bmps || !q || nframes == 0 || !chroma_ok(chroma)) return MYYUV_E_ARG;
+  for (uint32_t f = 0; f < nframes; f++)
+    if (!payloads[f] || !bmps[f]) return MYYUV_E_ARG;
+  if (int e = check_q(q)) return e;
+  for (uint32_t f = 0; f < nframes; f++)
+    if (int e = host_parse_headers(payloads[f], sizes[f])) return e;
+  uint32_t w = 0, h = 0;
+  ToBmp t{0, chroma, bit_count};
+  if (int e = bmp_check(width, height, bit_count, &w, &h, &t.orient)) return e;
+  return decompress_frames(c, payloads, sizes, nframes, w, h, q, bmps, bad_block, &t);
 }
 
 int myyuv_hip_profile(myyuv_hip_handle c, int enable) {

@@ -18,13 +18,14 @@ E_ARG, E_QUALITY, E_WIDTH, E_HEIGHT, E_CAPACITY = 1, 2, 3, 4, 5
 E_DCTYUV_SIZE, E_PLANE_SIZE, E_PLANE_NBLK, E_PLANE_CONTENT = 6, 7, 8, 9
 E_BAD_CODE, E_UNKNOWN_SYMBOL, E_BAD_CHUNK, E_HIP, E_NO_DEVICE = 10, 11, 12, 13, 14
 E_BMP_INVALID, E_BMP_SIGN, E_BMP_UNSUPPORTED = 15, 16, 17
+CHROMA_NEAREST, CHROMA_LINEAR = 0, 1  # MYYUV_CHROMA_*
 
 KERNELS = ["fdct_quant", "huff_encode", "scan_tiles", "stream_out", "encode_tile", "huff_decode",
            "dequant_idct", "huff_encode_wide", "huff_encode_r16", "huff_encode_wave", "bmp_to_iyuv",
-           "fdct_fix"]
+           "fdct_fix", "iyuv_to_bmp"]
 # ids: MYYUV_K_* of include/myyuv_hip.h, in KERNELS order (tests/test_cabi.py checks both)
 (K_FDCT, K_HUFF_ENC, K_SCAN, K_COMPACT, K_ENCODE_TILE, K_HUFF_DEC, K_IDCT, K_HUFF_WIDE,
- K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX) = range(len(KERNELS))
+ K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP) = range(len(KERNELS))
 
 # the exported symbols include/myyuv_hip.h declares (checked by the CPU tests)
 EXPORTS = [
@@ -35,7 +36,8 @@ EXPORTS = [
     "myyuv_gpu_huff_encode_blocks", "myyuv_hip_reserve_batch", "myyuv_gpu_dct_compress_batch_device",
     "myyuv_gpu_dct_decompress_batch_device", "myyuv_gpu_bmp_to_iyuv", "myyuv_gpu_bmp_to_iyuv_device",
     "myyuv_gpu_dct_compress_batch", "myyuv_gpu_dct_compress_frames", "myyuv_gpu_dct_decompress_frames",
-    "myyuv_gpu_dct_decompress_batch",
+    "myyuv_gpu_dct_decompress_batch", "myyuv_gpu_iyuv_to_bmp", "myyuv_gpu_iyuv_to_bmp_device",
+    "myyuv_gpu_dct_decompress_to_bmp", "myyuv_gpu_dct_decompress_to_bmp_frames",
 ]
 
 _lib = None
@@ -112,6 +114,13 @@ def load():
                                                   ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]
     L.myyuv_gpu_dct_compress_frames.argtypes = [vp, ctypes.POINTER(vp), u32, u32, u32, u8p, PAYLOAD_ALLOC, vp,
                                                 ctypes.POINTER(u32)]
+    u16 = ctypes.c_uint16
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    L.myyuv_gpu_iyuv_to_bmp.argtypes = [vp, u8p, i32, i32, u16, u32, u8p]
+    L.myyuv_gpu_iyuv_to_bmp_device.argtypes = [vp, vp, u32, i32, i32, u16, u32, vp, vp]
+    L.myyuv_gpu_dct_decompress_to_bmp.argtypes = [vp, u8p, u32, i32, i32, u8p, u16, u32, u8p, i64p]
+    L.myyuv_gpu_dct_decompress_to_bmp_frames.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u32), u32, i32, i32,
+                                                         u8p, u16, u32, ctypes.POINTER(vp), i64p]
     L.myyuv_debug_tinfo_guard.argtypes = [vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -339,6 +348,58 @@ class Codec:
                                                  int(bit_count), d_iyuv, stream)
         if rc:
             raise CodecError(rc)
+
+    def iyuv_to_bmp(self, iyuv, width, height, bit_count=32, chroma=CHROMA_LINEAR):
+        """IYUV frame -> the pixel array of a BMP with the signed header
+        fields `width` / `height` (the inverse of bmp_to_iyuv; the conversion
+        is defined in include/myyuv_hip.h)."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(iyuv).cast("B"), np.uint8))
+        W, H = abs(int(width)), abs(int(height))
+        if src.size < W * H * 3 // 2:
+            raise ValueError("frame smaller than |w|*|h|*3/2")
+        n = W * H * (int(bit_count) // 8)
+        out = np.empty(max(1, n), np.uint8)
+        rc = load().myyuv_gpu_iyuv_to_bmp(self._h, _u8(src), int(width), int(height), int(bit_count), int(chroma),
+                                          _u8(out))
+        if rc:
+            raise CodecError(rc)
+        return out[:n].tobytes()
+
+    def iyuv_to_bmp_device(self, d_iyuv, nframes, width, height, bit_count, chroma, d_bmp, stream=None):
+        rc = load().myyuv_gpu_iyuv_to_bmp_device(self._h, d_iyuv, int(nframes), int(width), int(height),
+                                                 int(bit_count), int(chroma), d_bmp, stream)
+        if rc:
+            raise CodecError(rc)
+
+    def decompress_to_bmp(self, payload, width, height, q, bit_count=32, chroma=CHROMA_LINEAR):
+        """DCTYUV payload -> BMP pixel array: decompress, then iyuv_to_bmp,
+        the frame staying on the device."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        n = abs(int(width)) * abs(int(height)) * (int(bit_count) // 8)
+        out = np.empty(max(1, n), np.uint8)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_decompress_to_bmp(self._h, _u8(src), src.size, int(width), int(height), _u8(_q(q)),
+                                                    int(bit_count), int(chroma), _u8(out), ctypes.byref(bad))
+        if rc:
+            raise CodecError(rc, bad.value)
+        return out[:n].tobytes()
+
+    def decompress_to_bmp_frames(self, payloads, width, height, q, bit_count=32, chroma=CHROMA_LINEAR):
+        """decompress_to_bmp for a list of payloads of one geometry and
+        quality (pipelined, as decompress_frames)."""
+        n = len(payloads)
+        ob = abs(int(width)) * abs(int(height)) * (int(bit_count) // 8)
+        srcs = [np.frombuffer(bytes(p), np.uint8) for p in payloads]
+        outs = [np.empty(max(1, ob), np.uint8) for _ in range(n)]
+        ip = (ctypes.c_void_p * n)(*[a.ctypes.data for a in srcs])
+        op = (ctypes.c_void_p * n)(*[a.ctypes.data for a in outs])
+        sizes = (ctypes.c_uint32 * n)(*[a.size for a in srcs])
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_decompress_to_bmp_frames(self._h, ip, sizes, n, int(width), int(height), _u8(_q(q)),
+                                                           int(bit_count), int(chroma), op, ctypes.byref(bad))
+        if rc:
+            raise CodecError(rc, bad.value)
+        return [o[:ob].tobytes() for o in outs]
 
     # -- device-resident API (pointers are device addresses, e.g. torch data_ptr) --
     def reserve(self, w, h):
