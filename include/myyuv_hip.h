@@ -209,6 +209,61 @@ int myyuv_gpu_dct_decompress_to_bmp(myyuv_hip_handle h, const uint8_t* payload, 
                                     int32_t height, const uint8_t quality[3], uint16_t bit_count,
                                     uint32_t chroma, uint8_t* bmp_data, int64_t* bad_block);
 
+/* Region decode: a rectangle of a compressed frame without decoding the rest.
+ * For a WxH frame and a region (rx, ry, rw, rh) in luma pixels, top-down frame
+ * coordinates, the result is the rw x rh IYUV frame
+ *   Y' = Y[ry : ry+rh, rx : rx+rw]
+ *   U' = U[ry/2 : (ry+rh)/2, rx/2 : (rx+rw)/2], V' likewise
+ * of the full decode, laid out as any IYUV frame (Y', U', V'; rw*rh*3/2
+ * bytes): byte for byte the crop of myyuv_gpu_dct_decompress's output.
+ * rx, ry, rw and rh are multiples of 16 (the reference's compress
+ * precondition for frames: every plane's rectangle is whole 8x8 blocks and
+ * the result is itself a compressible frame), rw, rh > 0, rx+rw <= W and
+ * ry+rh <= H (no 32-bit wrap); anything else is MYYUV_E_ARG.
+ * Checks and errors: the handle, pointer, quality, stream-header and % 8
+ * dimension checks of myyuv_gpu_dct_decompress, in its order, then the
+ * region's.  The chunk-size table of the whole frame is still scanned (its
+ * prefix sums place the region's chunks), so header errors are unchanged; of
+ * the chunks only the region's are read.  A malformed chunk OUTSIDE the region
+ * is therefore not reported and the region decodes: that is the point of the
+ * call, not an omission.  A malformed chunk inside it gives the full decode's
+ * code, *bad_block its index in the FULL frame's numbering (plane-major,
+ * row-major), the lowest such index when there are several; the
+ * plane-content check (MYYUV_E_PLANE_CONTENT) applies to the region's blocks.
+ * Workspace: 4 B per block of the full frame (the scan), nothing of the
+ * 471 B per block the other calls reserve.  The host-buffer forms copy the
+ * whole payload to the device and rw*rh*3/2 (or the region's BMP) bytes back. */
+int myyuv_gpu_dct_decompress_region(myyuv_hip_handle h, const uint8_t* payload, uint32_t size,
+                                    uint32_t width, uint32_t height, const uint8_t quality[3],
+                                    uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh,
+                                    uint8_t* iyuv, int64_t* bad_block);
+/* Device-resident batch: stream f at d_payload + f*cap (cap a multiple of 4
+ * when nframes > 1, its size at d_payload_sizes[f]) -> region frame f at
+ * d_iyuv + f*rw*rh*3/2; one region for all frames; asynchronous on `stream`
+ * (NULL = the context's); argument errors are returned at once, device-side
+ * errors through myyuv_hip_sync_status (batch-global block index
+ * f * blocks_per_frame + block, blocks of the full frame). */
+int myyuv_gpu_dct_decompress_region_device(myyuv_hip_handle h, const void* d_payload,
+                                           const uint32_t* d_payload_sizes, uint32_t cap, uint32_t nframes,
+                                           uint32_t width, uint32_t height, const uint8_t quality[3],
+                                           uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh,
+                                           void* d_iyuv, void* stream);
+/* Region decode and K8 on the device: by definition myyuv_gpu_iyuv_to_bmp of
+ * the region's frame.  width / height are signed as in
+ * myyuv_gpu_dct_decompress_to_bmp: their magnitudes are the frame's size,
+ * their signs the orientation of the BMP written; the region is unsigned,
+ * in top-down frame coordinates; the output is rw x rh pixels
+ * (rw*rh*bit_count/8 bytes).  Under MYYUV_CHROMA_NEAREST this is the crop of
+ * the full frame's picture.  Under MYYUV_CHROMA_LINEAR the chroma clamp is
+ * at the REGION's edge, so the outermost ring of pixels can differ from the
+ * full picture's.  Errors as myyuv_gpu_dct_decompress_to_bmp, then the
+ * region's. */
+int myyuv_gpu_dct_decompress_region_to_bmp(myyuv_hip_handle h, const uint8_t* payload, uint32_t size,
+                                           int32_t width, int32_t height, const uint8_t quality[3],
+                                           uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh,
+                                           uint16_t bit_count, uint32_t chroma, uint8_t* bmp_data,
+                                           int64_t* bad_block);
+
 /* Host-buffer batches (many frames per call; §7 step 9:
  * transfers overlapped with the kernels).  The batch runs in chunks of up to
  * 8 frames through two device slots: chunk k's host -> device copies, chunk
@@ -275,7 +330,8 @@ int myyuv_hip_sync_status(myyuv_hip_handle h, void* stream, int64_t* bad_block);
 #define MYYUV_K_BMP 10       /* K7 bmp_to_iyuv (BMP -> IYUV conversion) */
 #define MYYUV_K_FDCT_FIX 11  /* K1's exact path for the units K1 listed (fdct_fix) */
 #define MYYUV_K_IYUV_BMP 12  /* K8 iyuv_to_bmp (IYUV -> BMP conversion) */
-#define MYYUV_K_COUNT 13
+#define MYYUV_K_REGION 13    /* fused decoder of a rectangle of the frame (decode_region) */
+#define MYYUV_K_COUNT 14
 int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 /* As myyuv_hip_profile, but stamps only the kernels whose bit (1 << MYYUV_K_*)
  * is set in `mask` (0 disables): event stamping costs host and queue time per

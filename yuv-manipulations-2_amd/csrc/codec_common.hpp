@@ -139,6 +139,18 @@ struct FrameGeom {
 // groups) stays below 4 GiB, the range of the kernels' 32-bit buffer offsets.
 constexpr uint32_t kMaxLaunchBlocks = (1u << 25) - 64u;
 
+// A rectangle of whole blocks of a frame, as k_decode_region sees it: per
+// plane the rectangle's first block column / row in the SOURCE frame, and
+// its work list: a segment is a run of at most kWave consecutive blocks of one
+// block row of the rectangle, numbered plane-major, row-major, left to right
+// (plane p owns segments [scum[p], scum[p+1]), spr[p] per row).  The
+// rectangle's own size is the FrameGeom of the output frame.
+struct RegionSegs {
+  uint32_t bx[3], by[3];
+  uint32_t spr[3];
+  uint32_t scum[4];
+};
+
 // floor(x / d) for a 32-bit x from m = ceil(2^64 / d) (m = 0 for d = 1): the
 // product overshoots x / d by less than x / 2^64, below the 1 / d slack.
 __host__ __device__ __forceinline__ uint32_t div_magic(uint32_t x, uint64_t m) {

@@ -12,6 +12,11 @@
 // the way back, which the reference leaves to its viewers (K8; a compressed
 // input is decoded and converted on the device):
 //   myyuv_cli in.myyuv -to_bmp [24|32] [-chroma nearest|linear] -o out.bmp
+// a region of the frame only (region decode, include/myyuv_hip.h: of a
+// compressed input only the region's chunks are decoded; an uncompressed
+// input is cropped on the host):
+//   myyuv_cli in.myyuv -decompress -crop X Y W H -o out.myyuv
+//   myyuv_cli in.myyuv -to_bmp [24|32] [-chroma nearest|linear] -crop X Y W H -o out.bmp
 // and, beyond the reference CLI, many frames per invocation (SURVEY.md §8f
 // row 2; frames of one geometry share batched kernel launches):
 //   myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IN.myyuv...
@@ -44,14 +49,32 @@ void usage() {
             << "Usage:\n"
             << "  myyuv_cli IMAGE.myyuv -info\n"
             << "  myyuv_cli IMAGE.myyuv -compress DCT Q [Q [Q]] -o OUT.myyuv   (Q in 1..100, per plane Y U V)\n"
-            << "  myyuv_cli IMAGE.myyuv -decompress -o OUT.myyuv\n"
-            << "  myyuv_cli IMAGE.myyuv -to_bmp [24|32] [-chroma nearest|linear] -o OUT.bmp\n"
+            << "  myyuv_cli IMAGE.myyuv -decompress [-crop X Y W H] -o OUT.myyuv\n"
+            << "  myyuv_cli IMAGE.myyuv -to_bmp [24|32] [-chroma nearest|linear] [-crop X Y W H] -o OUT.bmp\n"
+            << "      (-crop: only that region, luma pixels from the top-left, multiples of 16)\n"
             << "  myyuv_cli IMAGE.bmp -info\n"
             << "  myyuv_cli IMAGE.bmp -to_yuv IYUV -o OUT.myyuv\n"
             << "  myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IMAGE.myyuv...\n"
             << "  myyuv_cli -batch-decompress -o OUTDIR IMAGE.myyuv...\n"
             << "\nYUV formats:\nIYUV\n\nCompression formats for YUV:\nDCT\n"
             << "\nExample:\n  myyuv_cli image.myyuv -compress DCT 50 -o image-DCT-50.myyuv\n";
+}
+
+constexpr const char* kCropHelp = "Invalid argument, -crop must be followed by four numbers `X Y W H`\n";
+
+// `-crop X Y W H` at args[a]: four unsigned decimal numbers into r, a moved
+// past them.  false: fewer than four, or one that is not a 32-bit number.
+bool parse_crop(const std::vector<std::string>& args, size_t& a, uint32_t r[4]) {
+  if (a + 4 >= args.size()) return false;
+  for (int i = 0; i < 4; i++) {
+    const std::string& v = args[a + 1 + i];
+    if (v.empty() || v.size() > 10 || v.find_first_not_of("0123456789") != std::string::npos) return false;
+    const unsigned long long x = std::stoull(v);
+    if (x > 0xFFFFFFFFull) return false;
+    r[i] = (uint32_t)x;
+  }
+  a += 5;
+  return true;
 }
 
 myyuv::YUV compress_dct(const myyuv::YUV& yuv, const std::vector<std::string>& params) {
@@ -109,11 +132,20 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     return 0;
   }
   if (cmd == "-decompress") {
-    if (!yuv.isCompressed()) {
+    // [-crop X Y W H]: the region only (a compressed image: region decode on
+    // the GPU; an uncompressed one: its rows copied on the host)
+    const bool crop = a + 1 < args.size() && args[a + 1] == "-crop";
+    if (!crop && !yuv.isCompressed()) {
       std::cout << "Nothing to decompress, image is not compressed\n";
       return 1;
     }
     a++;
+    uint32_t r[4] = {0, 0, 0, 0};
+    if (crop && !parse_crop(args, a, r)) {
+      std::cout << kCropHelp;
+      usage();
+      return 1;
+    }
     if (args.size() != a + 2) {
       std::cout << "Invalid arguments amount. " << (a + 2) << " is required\n";
       usage();
@@ -125,8 +157,18 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
       return 1;
     }
     myyuv::YUV out;
-    const float ms = elapsed_ms([&] { out = yuv.decompress(); });
-    std::cout << "YUV DCT decompression : " << ms << " ms\n";
+    const float ms = elapsed_ms([&] {
+      if (!crop)
+        out = yuv.decompress();
+      else if (yuv.isCompressed())
+        out = myyuvDCT::decompress_DCT_planar_region(yuv, r[0], r[1], r[2], r[3]);
+      else
+        out = myyuv::crop_region(yuv, r[0], r[1], r[2], r[3]);
+    });
+    if (crop)
+      std::cout << "YUV crop (" << r[0] << " " << r[1] << " " << r[2] << " " << r[3] << ") : " << ms << " ms\n";
+    else
+      std::cout << "YUV DCT decompression : " << ms << " ms\n";
     out.dump(args[a + 1]);
     return 0;
   }
@@ -135,7 +177,7 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     uint16_t bits = 32;
     uint32_t chroma = 1;  // MYYUV_CHROMA_LINEAR
     std::string mode = "linear";
-    if (a < args.size() && args[a] != "-o" && args[a] != "-chroma") {
+    if (a < args.size() && args[a] != "-o" && args[a] != "-chroma" && args[a] != "-crop") {
       if (args[a] != "24" && args[a] != "32") {
         std::cout << "Invalid bit count " << args[a] << ", must be 24 or 32\n";
         usage();
@@ -153,13 +195,22 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
       chroma = mode == "linear" ? 1 : 0;
       a += 2;
     }
+    uint32_t r[4] = {0, 0, 0, 0};
+    const bool crop = a < args.size() && args[a] == "-crop";
+    if (crop && !parse_crop(args, a, r)) {
+      std::cout << kCropHelp;
+      usage();
+      return 1;
+    }
     if (args.size() != a + 2 || args[a] != "-o") {
       std::cout << "Invalid argument, last arguments must be `-o /path/to/new_image.bmp`\n";
       usage();
       return 1;
     }
     myyuv::BMP out;
-    const float ms = elapsed_ms([&] { out = myyuv::yuv_to_bmp(yuv, bits, chroma); });
+    const float ms = elapsed_ms([&] {
+      out = crop ? myyuv::yuv_to_bmp(yuv, r[0], r[1], r[2], r[3], bits, chroma) : myyuv::yuv_to_bmp(yuv, bits, chroma);
+    });
     std::cout << "YUV to BMP (" << bits << " " << mode << ") : " << ms << " ms\n";
     out.dump(args[a + 1]);
     return 0;

@@ -295,12 +295,39 @@ void YUV::dump(const std::string& path) const {
   f.write(reinterpret_cast<const char*>(data), header.data_size);
 }
 
-BMP yuv_to_bmp(const YUV& yuv, uint16_t bit_count, uint32_t chroma) {
+namespace {
+
+// The region checks of include/myyuv_hip.h (region decode), for the paths
+// that crop on the host.
+void check_region(uint32_t w, uint32_t h, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh) {
+  if (((rx | ry | rw | rh) & 15u) || rw == 0 || rh == 0 || (uint64_t)rx + rw > w || (uint64_t)ry + rh > h)
+    fail(MYYUV_E_ARG);
+}
+
+// Header of the region's frame: decompress_DCT_planar's rewrite (DCT.cpp:446-453)
+// with the region's size.
+YUVHeader region_header(const YUVHeader& in, uint32_t rw, uint32_t rh) {
+  YUVHeader h = in;
+  h.compression = YUV::Compressions::NONE;
+  h.compression_params_size = 0;
+  h.compression_params_pos = 0;
+  h.data_pos = sizeof(YUVHeader);
+  h.width = rw;
+  h.height = rh;
+  h.data_size = (uint32_t)((uint64_t)rw * rh * 3 / 2);
+  return h;
+}
+
+// yuv_to_bmp of the whole frame (region == nullptr) or of region[0..3] = (rx, ry, rw, rh).
+BMP to_bmp(const YUV& yuv, const uint32_t* region, uint16_t bit_count, uint32_t chroma) {
   static_assert(MYYUV_CHROMA_LINEAR == 1, "the header's default chroma mode");
   if (!yuv.isValid()) throw std::runtime_error("YUV is invalid");
   if (yuv.getFourccFormat() != YUV::FourccFormats::IYUV) throw std::runtime_error("Incorrect format");
   if (bit_count != 24 && bit_count != 32) fail(MYYUV_E_BMP_UNSUPPORTED);
-  const uint32_t w = yuv.header.width, h = yuv.header.height;
+  const uint32_t fw = yuv.header.width, fh = yuv.header.height;
+  if (region && yuv.getCompression() == YUV::Compressions::NONE) check_region(fw, fh, region[0], region[1], region[2], region[3]);
+  // (a compressed frame's region is checked by the C ABI, after the stream's header)
+  const uint32_t w = region ? region[2] : fw, h = region ? region[3] : fh;
   // BMP::imageSize(), file_size and dump() hold the pixel array's size in 32
   // bits, and imageSize() forms w * h * bit_count before it divides: an image
   // past that cannot be a BMP (and a wrapped size would under-allocate `data`)
@@ -320,18 +347,59 @@ BMP yuv_to_bmp(const YUV& yuv, uint16_t bit_count, uint32_t chroma) {
   res.data = new uint8_t[bytes ? bytes : 1];
   int rc;
   if (yuv.getCompression() == YUV::Compressions::NONE) {
-    if (yuv.header.data_size < (uint64_t)w * h * 3 / 2) throw std::runtime_error("YUV is invalid");
-    rc = myyuv_gpu_iyuv_to_bmp(t_codec.get(), yuv.data, bh.width, bh.height, bit_count, chroma, res.data);
+    if (yuv.header.data_size < (uint64_t)fw * fh * 3 / 2) throw std::runtime_error("YUV is invalid");
+    if (region) {
+      const YUV part = crop_region(yuv, region[0], region[1], region[2], region[3]);
+      rc = myyuv_gpu_iyuv_to_bmp(t_codec.get(), part.data, bh.width, bh.height, bit_count, chroma, res.data);
+    } else {
+      rc = myyuv_gpu_iyuv_to_bmp(t_codec.get(), yuv.data, bh.width, bh.height, bit_count, chroma, res.data);
+    }
   } else if (yuv.getCompression() == YUV::Compressions::DCT) {
     if (yuv.header.compression_params_size != 3)
       throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
     int64_t bad = -1;
-    rc = myyuv_gpu_dct_decompress_to_bmp(t_codec.get(), yuv.data, yuv.header.data_size, bh.width, bh.height,
-                                         yuv.compression_params, bit_count, chroma, res.data, &bad);
+    if (fw > 0x7FFFFFFFu || fh > 0x7FFFFFFFu) fail(MYYUV_E_ARG);
+    rc = region ? myyuv_gpu_dct_decompress_region_to_bmp(t_codec.get(), yuv.data, yuv.header.data_size, (int32_t)fw,
+                                                         (int32_t)fh, yuv.compression_params, region[0], region[1],
+                                                         region[2], region[3], bit_count, chroma, res.data, &bad)
+                : myyuv_gpu_dct_decompress_to_bmp(t_codec.get(), yuv.data, yuv.header.data_size, bh.width, bh.height,
+                                                  yuv.compression_params, bit_count, chroma, res.data, &bad);
   } else {
     throw std::runtime_error("Error this decompression is unimplemented");
   }
   if (rc) fail(rc);
+  return res;
+}
+
+}  // namespace
+
+BMP yuv_to_bmp(const YUV& yuv, uint16_t bit_count, uint32_t chroma) { return to_bmp(yuv, nullptr, bit_count, chroma); }
+
+BMP yuv_to_bmp(const YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh, uint16_t bit_count,
+               uint32_t chroma) {
+  const uint32_t region[4] = {rx, ry, rw, rh};
+  return to_bmp(yuv, region, bit_count, chroma);
+}
+
+YUV crop_region(const YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh) {
+  if (!yuv.isValid()) throw std::runtime_error("YUV is invalid");
+  if (yuv.getFourccFormat() != YUV::FourccFormats::IYUV) throw std::runtime_error("Incorrect format");
+  if (yuv.getCompression() != YUV::Compressions::NONE) throw std::runtime_error("Error. The image is compressed");
+  const uint32_t w = yuv.header.width, h = yuv.header.height;
+  if (yuv.header.data_size < (uint64_t)w * h * 3 / 2) throw std::runtime_error("YUV is invalid");
+  check_region(w, h, rx, ry, rw, rh);
+  YUV res;
+  res.header = region_header(yuv.header, rw, rh);
+  res.data = new uint8_t[res.header.data_size];
+  const uint8_t* src = yuv.data;
+  uint8_t* dst = res.data;
+  for (int p = 0; p < 3; p++) {  // Y, then U and V at half size
+    const uint32_t sh = p ? 1 : 0;
+    const size_t pw = w >> sh, ph = h >> sh, cw = rw >> sh, ch = rh >> sh;
+    for (size_t y = 0; y < ch; y++) std::memcpy(dst + y * cw, src + ((ry >> sh) + y) * pw + (rx >> sh), cw);
+    src += pw * ph;
+    dst += cw * ch;
+  }
   return res;
 }
 
@@ -502,8 +570,36 @@ myyuv::YUV decompress_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t
   return res;
 }
 
+// The region of a compressed frame: decompress_DCT_planar's checks and header
+// with the region's size; the C ABI checks the region after the stream's
+// header and decodes nothing outside it.
+myyuv::YUV decompress_DCT_planar_region(const myyuv::YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh) {
+  using myyuv::YUV;
+  if (yuv.getFormatGroup() != YUV::FormatGroup::PLANAR)
+    throw std::runtime_error("Error decompressing: YUV must be planar");
+  if (yuv.getCompression() != YUV::Compressions::DCT)
+    throw std::runtime_error("Error this decompression is unimplemented");
+  if (yuv.header.compression_params_size != 3 || !yuv.compression_params)
+    throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
+  for (int p = 0; p < 3; p++)
+    if (yuv.compression_params[p] < 1 || yuv.compression_params[p] > 100)
+      throw std::runtime_error("Level of quality must be between 1 and 100");
+  YUV res;
+  res.header = myyuv::region_header(yuv.header, rw, rh);
+  // (a region the C ABI will refuse may be larger than the frame: no buffer for it)
+  const bool fits = (uint64_t)rw * rh <= (uint64_t)yuv.header.width * yuv.header.height;
+  res.data = new uint8_t[fits && res.header.data_size ? res.header.data_size : 1];
+  int64_t bad = -1;
+  const int rc = fits ? myyuv_gpu_dct_decompress_region(t_codec.get(), yuv.data, yuv.header.data_size,
+                                                        yuv.header.width, yuv.header.height, yuv.compression_params,
+                                                        rx, ry, rw, rh, res.data, &bad)
+                      : MYYUV_E_ARG;
+  if (rc) fail(rc);
+  return res;
+}
 
-// Many compressed frames per call.  Each frame is checked as YUV::decompress
+
+// Many compressed frames per call. Each frame is checked as YUV::decompress
 // -> decompress_map[DCT][IYUV] -> decompress_DCT_planar would, in input order
 // (frames that are not DCT / IYUV, or fail a check, take that single-frame
 // path and its error); the DCT frames of one geometry and quality triple

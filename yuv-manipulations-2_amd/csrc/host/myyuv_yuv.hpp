@@ -107,6 +107,17 @@ class YUV {
 // uncompressed frame goes through myyuv_gpu_iyuv_to_bmp, a DCT-compressed one
 // through myyuv_gpu_dct_decompress_to_bmp (decoded and converted on the device).
 BMP yuv_to_bmp(const YUV& yuv, uint16_t bit_count = 32, uint32_t chroma = 1 /* MYYUV_CHROMA_LINEAR */);
+// The same for the region (rx, ry, rw, rh) of the frame (luma pixels, top-down,
+// multiples of 16, inside the frame: include/myyuv_hip.h, region decode): a
+// rw x rh BMP, by definition the conversion of the region's frame.  A
+// DCT-compressed frame goes through myyuv_gpu_dct_decompress_region_to_bmp
+// (only the region is decoded), an uncompressed one is cropped on the host.
+BMP yuv_to_bmp(const YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh, uint16_t bit_count = 32,
+               uint32_t chroma = 1 /* MYYUV_CHROMA_LINEAR */);
+// The region of an UNCOMPRESSED planar frame, rows copied on the host: the
+// frame myyuvDCT::decompress_DCT_planar_region returns for the compressed
+// form of the same pixels (same constraints, same header, same bytes).
+YUV crop_region(const YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh);
 
 }  // namespace myyuv
 
@@ -114,6 +125,11 @@ namespace myyuvDCT {
 // myyuv_DCT/DCT.hpp:16,25 — same signatures, HIP implementation.
 myyuv::YUV compress_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 3>& params);
 myyuv::YUV decompress_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 3>& params);
+// Region decode (include/myyuv_hip.h): the rw x rh frame cropped from the full
+// decode at (rx, ry), of which only the region's chunks are read.  The quality
+// bytes are the frame's compression parameters; the header is
+// decompress_DCT_planar's with width = rw, height = rh, data_size = rw*rh*3/2.
+myyuv::YUV decompress_DCT_planar_region(const myyuv::YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh);
 // Many frames per call: frames of one geometry share
 // one batched launch of every kernel; result i is compress_DCT_planar(*frames[i]).
 std::vector<myyuv::YUV> compress_DCT_planar_batch(const std::vector<const myyuv::YUV*>& frames,

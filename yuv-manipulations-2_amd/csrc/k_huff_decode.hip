@@ -273,13 +273,14 @@ __device__ __forceinline__ bool decode_regular(const LdsChunk& c, const Table& T
 
 // Symbols of any table, bit-serial conditions as the reference evaluates them
 // (uint8 arithmetic of `first` kept), values found by walking the groups of
-// the matched length in stream order; int16 stores straight into the quad
-// layout (slot `g`), zeros after the last symbol.  Only lanes whose table is
-// not regular (malformed or hand-made streams) come here, after the wave's
-// regular lanes, with the unrolled state dead.
-__device__ __forceinline__ int decode_general(const LdsChunk c, const Table T, uint4* coef,
-                                           uint32_t g) {
-  uint16_t* out = reinterpret_cast<uint16_t*>(coef);
+// the matched length in stream order; every coefficient is handed to put(z, v)
+// (int16 v at natural index z), zeros after the last symbol: decode_general
+// stores them straight into the quad layout (slot `g`), the region decoder
+// into LDS.  Only lanes whose table is not regular (malformed or hand-made
+// streams) come here, after the wave's regular lanes, with the unrolled state
+// dead.
+template <class Put>
+__device__ __forceinline__ int decode_general_to(const LdsChunk c, const Table T, Put put) {
   int code = 0;
   uint32_t bp = 0, j = 0;
   while (bp < T.nbits && j < 64) {
@@ -321,15 +322,21 @@ __device__ __forceinline__ int decode_general(const LdsChunk c, const Table T, u
       i += 1 + (n * 11 + 7) / 8;
     }
     const uint32_t z = c_zz_dev[j];
-    out[coef_quad(g, z >> 3) * 8 + (z & 7)] = (uint16_t)(((int32_t)(c.bits32(vbit) << 21)) >> 21);
+    put(z, (uint16_t)(((int32_t)(c.bits32(vbit) << 21)) >> 21));
     bp += mL;
     j++;
   }
   for (; j < 64; j++) {
     const uint32_t z = c_zz_dev[j];
-    out[coef_quad(g, z >> 3) * 8 + (z & 7)] = 0;
+    put(z, (uint16_t)0);
   }
   return code;
+}
+
+__device__ __forceinline__ int decode_general(const LdsChunk c, const Table T, uint4* coef,
+                                           uint32_t g) {
+  uint16_t* out = reinterpret_cast<uint16_t*>(coef);
+  return decode_general_to(c, T, [=](uint32_t z, uint16_t v) { out[coef_quad(g, z >> 3) * 8 + (z & 7)] = v; });
 }
 
 }  // namespace
@@ -756,6 +763,293 @@ __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_idct(const uint8_
   for (int k = 0; k < 8; k++)
     if (lane == (uint32_t)k && wid < 65536) g_dec_wstamps[wid * 8 + k] = dst.acc[k];
 #endif
+}
+
+// ---- region decode --------------------------------------------------------
+//
+// k_decode_region: the fused decoder for a rectangle of whole blocks of the
+// frame (RegionSegs, codec_common.hpp).  One wave per segment (blockIdx.x) of
+// frame blockIdx.y: a run of up to 64 consecutive blocks of one block row, so
+// its chunks are one contiguous byte range of the plane's content, as a
+// group's are.  The run starts anywhere in its 64-block group and may cross
+// into the next one; k_scan_chain keeps offsets at group starts only, so with
+// j the run's first block inside the plane its first chunk is at
+//   scanned(cum_p + (j & ~63)) - scanned(cum_p) + sum of the sizes of [j & ~63, j)
+// (the sum: one masked load of up to 63 size bytes and a wave scan), and lane
+// l's chunk follows by the exclusive scan of the run's own sizes.  Only the
+// size bytes and the run's chunks are read: a malformed chunk outside the
+// rectangle is never seen.  The rows go into a frame of the rectangle's own
+// geometry (R); error keys name the SOURCE frame's blocks.
+//
+// decode_run is decode_group's sibling (a copy of its rounds with the setup
+// above in front: the two existing decoders compile to what they did).  It
+// differs in three places: the size bytes are needed for the first chunk's
+// position, so round 1's loads go out after them; the end of the run's
+// bytes comes from the wave's own scan; and blocks with a table that is not
+// "regular" are decoded (decode_general_to) into the value-position table's
+// 2 KiB of LDS, dead by then, 16 lanes at a time, and read back into nw: the
+// region path has no coefficient buffer in HBM.
+struct DecodeRun {
+  uint32_t f;
+  int p;
+  uint32_t jo0, n;  // the run's first block in the OUTPUT plane, its length
+  bool live;
+};
+__device__ __forceinline__ bool decode_run(const uint8_t* __restrict__ in, const uint32_t* __restrict__ in_size,
+                                           uint32_t cap, const StreamDesc* __restrict__ desc,
+                                           const uint32_t* __restrict__ local_off,
+                                           const uint32_t* __restrict__ tile_pre, const FrameGeom& G,
+                                           const FrameGeom& R, const RegionSegs& S,
+                                           unsigned long long* __restrict__ err, uint4* stq, DecodeRun& D,
+                                           uint32_t (&nw)[32]) {
+  const uint32_t f = blockIdx.y;
+  const uint32_t nblk = G.cum[3];
+  const uint32_t gbase = f * nblk;
+  const uint32_t ntiles = (nblk + kScanTile - 1) / kScanTile;
+  in += (size_t)f * cap;
+  desc += f;
+  local_off += gbase;
+  tile_pre += (size_t)f * (ntiles + 1);
+  const uint32_t lane = threadIdx.x;
+  uint32_t* gtab = reinterpret_cast<uint32_t*>(stq + kStageQuads + 1);
+  uint32_t* gcol = gtab + lane;
+  const uint32_t t = blockIdx.x;
+  const int p = t >= S.scum[1] ? (t >= S.scum[2] ? 2 : 1) : 0;
+  auto sel3 = [p](uint32_t a0, uint32_t a1, uint32_t a2) { return p == 0 ? a0 : (p == 1 ? a1 : a2); };
+  const uint32_t cum_p = sel3(G.cum[0], G.cum[1], G.cum[2]);
+  const uint32_t spr = sel3(S.spr[0], S.spr[1], S.spr[2]);
+  const uint32_t ts = t - sel3(0u, S.scum[1], S.scum[2]);
+  const uint32_t row = ts / spr, k = ts - row * spr;
+  const uint32_t rbw = sel3(R.bw[0], R.bw[1], R.bw[2]), sbw = sel3(G.bw[0], G.bw[1], G.bw[2]);
+  const uint32_t n = min((uint32_t)kWave, rbw - kWave * k);
+  // the run's first block inside the source plane, its group's first, and
+  // the group's blocks in front of the run
+  const uint32_t j = (sel3(S.by[0], S.by[1], S.by[2]) + row) * sbw + sel3(S.bx[0], S.bx[1], S.bx[2]) + kWave * k;
+  const uint32_t jg = j & ~(uint32_t)(kWave - 1), npre = j - jg;
+  const bool live = lane < n;
+  const uint32_t g = cum_p + j + lane;  // the lane's block in the source frame
+  const StreamDesc dsc = *desc;
+  const uint32_t isz = in_size[f];
+  const uint32_t lo_p = local_off[cum_p], tp_p = tile_pre[cum_p / kScanTile];
+  const uint32_t lo_g = local_off[cum_p + jg], tp_g = tile_pre[(cum_p + jg) / kScanTile];
+  __builtin_amdgcn_sched_barrier(0);  // (all issued before the first use waits)
+  const bool bad = dsc.bad != 0;
+  const uint32_t limit = bad ? 0u : min(isz, cap);
+  const uint32_t cpos = sel3(dsc.content_pos[0], dsc.content_pos[1], dsc.content_pos[2]);
+  const uint32_t csize = sel3(dsc.content_size[0], dsc.content_size[1], dsc.content_size[2]);
+  const uint32_t spos = sel3(dsc.sizes_pos[0], dsc.sizes_pos[1], dsc.sizes_pos[2]);
+  // the lane's own size byte and the size byte of block jg + lane in front of
+  // the run, loaded together (both inside the plane's size table: the header
+  // checks passed, or `bad` and byte 0)
+  const uint32_t s = in[bad ? 0u : spos + j + (live ? lane : n - 1u)];
+  const uint32_t sp = in[bad ? 0u : spos + jg + (lane < npre ? lane : 0u)];
+  const uint32_t incl = wave_incl_scan(live ? s : 0u);
+  const uint32_t pincl = wave_incl_scan(lane < npre ? sp : 0u);
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  const uint32_t pre0 = (lo_g + tp_g) - (lo_p + tp_p) + (uint32_t)__builtin_amdgcn_readlane((int)pincl, 63);
+  const uint32_t rel = pre0 + incl - (live ? s : 0u);
+  // end of the run's chunk range, inside the declared content
+  const uint32_t E = cpos + min(pre0 + total, csize);
+  auto window = [&](uint32_t A, uint32_t& aw, uint32_t& wend, uint32_t& nq, uint32_t& nfull) {
+    aw = A & ~15u;
+    wend = aw + 16 * (kStageQuads - 1);
+    nq = E > aw ? (min(E, wend) - aw + 15) >> 4 : 0u;
+    nfull = limit >= aw ? min(nq, (limit - aw) >> 4) : 0u;  // quads below limit
+  };
+  auto load4 = [&](uint32_t aw, uint32_t nfull) {  // (as decode_group's: every address below `limit`)
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+      const uint8_t* src = nfull > 0 ? in + aw + 16 * min(lane + 64u * m, nfull - 1) : in;
+      __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(stq + 64 * m),
+                                       16, 0, 0);
+    }
+  };
+  uint32_t aw, wend, nq, nfull;
+  window(cpos + pre0, aw, wend, nq, nfull);
+  load4(aw, nfull);
+
+  // plane-level check, for the rectangle's blocks
+  bool ok = live && !bad;
+  if (ok && rel + s > csize) {
+    record_error(err, 2ull * ((uint64_t)G.fbase * nblk + gbase + cum_p), 9 /* MYYUV_E_PLANE_CONTENT */);
+    ok = false;
+  }
+
+  int code = 0;
+  uint64_t pending = __ballot(ok);
+  auto stage = [&]() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // load4's LDS writes (before the zero quads)
+    for (uint32_t q = lane + 256; q < nfull; q += 64)
+      stq[q] = *reinterpret_cast<const uint4*>(in + aw + 16 * q);
+    for (uint32_t q = nfull + lane; q <= nq; q += 64) {
+      uint32_t v[4] = {0, 0, 0, 0};
+      if (q < nq) {
+#pragma unroll
+        for (uint32_t b = 0; b < 16; b++) {
+          const uint32_t a = aw + 16 * q + b;
+          if (a < limit) v[b >> 2] |= (uint32_t)in[a] << (8 * (b & 3));
+        }
+      }
+      stq[q] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+    __syncthreads();
+  };
+  if (pending) stage();
+  while (pending) {
+    const bool mine = ((pending >> lane) & 1) && cpos + rel + s <= wend;
+    const LdsChunk lc{reinterpret_cast<const uint32_t*>(stq), mine ? cpos + rel - aw : 0u};
+    Table T;
+    const int pcode = parse_table(lc, mine ? s : 0u, T, gcol);
+    const bool go = mine && pcode == 0;
+    int dcode = 0;
+    const bool failed = decode_regular(lc, T, gcol, go && T.regular, nw);
+    // the bit-serial path (tables the reference never writes, and failed
+    // messages for the reference's exact code), 16 lanes at a time: lane of
+    // rank r among them owns 128 B (64 int16, natural order) at 128 r of the
+    // value-position table, which the next round's parse rewrites
+    uint64_t dm = __ballot(go && (!T.regular || failed));
+    while (dm) {
+      const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0u));
+      const bool sel = ((dm >> lane) & 1) && rk < 16u;
+      if (sel) {
+        uint16_t* slot = reinterpret_cast<uint16_t*>(gtab) + 64u * rk;
+        dcode = decode_general_to(lc, T, [=](uint32_t z, uint16_t v) { slot[z] = v; });
+        const uint4* img = reinterpret_cast<const uint4*>(slot);
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+          const uint4 v = img[c];
+          nw[4 * c] = v.x;
+          nw[4 * c + 1] = v.y;
+          nw[4 * c + 2] = v.z;
+          nw[4 * c + 3] = v.w;
+        }
+      }
+      dm &= ~__ballot(sel);
+    }
+    if (mine) code = go ? dcode : pcode;
+    pending &= ~__ballot(mine);
+    if (pending) {  // the next round, from the lowest pending lane's chunk
+      __syncthreads();  // it overwrites the stage
+      const int lo = __ffsll((long long)pending) - 1;
+      window(cpos + __shfl(rel, lo, 64), aw, wend, nq, nfull);
+      load4(aw, nfull);
+      stage();
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every LDS-DMA load has landed (whether or not a round ran)
+  if (ok && code) record_error(err, 2ull * ((uint64_t)G.fbase * nblk + gbase + g) + 1, code);
+  D.f = f;
+  D.p = p;
+  D.jo0 = row * rbw + kWave * k;
+  D.n = n;
+  D.live = live;
+  return !bad;
+}
+
+__global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_region(const uint8_t* __restrict__ in,
+                                                     const uint32_t* __restrict__ in_size,
+                                                     uint32_t cap,
+                                                     const StreamDesc* __restrict__ desc,
+                                                     const uint32_t* __restrict__ local_off,
+                                                     const uint32_t* __restrict__ tile_pre,
+                                                     FrameGeom G, FrameGeom R, RegionSegs S,
+                                                     const QTables* __restrict__ qt,
+                                                     uint8_t* __restrict__ frame,
+                                                     unsigned long long* __restrict__ err) {
+  static_assert(sizeof(uint4) * kStageQuads >= sizeof(float) * xf::kXfTile16, "the tile over the stage");
+  static_assert(kGposQuads * 16 >= 16 * 128, "16 blocks of int16[64] in the value-position table");
+  __shared__ uint4 stq[kStageQuads + 1 + kGposQuads];
+  __shared__ float sq[64];
+  __shared__ uint16_t s_blk[64];
+  const uint32_t lane = threadIdx.x;
+  if (lane == 0) stq[kStageQuads] = make_uint4(0u, 0u, 0u, 0u);  // (ordered by decode_run's barrier)
+  {
+    // the plane's Q table by LDS-DMA (landed by decode_run's final vmcnt wait)
+    const uint32_t t = blockIdx.x;
+    const int p = t >= S.scum[1] ? (t >= S.scum[2] ? 2 : 1) : 0;
+    __builtin_amdgcn_global_load_lds((const void*)&qt->q[p][lane], (__attribute__((address_space(3))) void*)sq, 4,
+                                     0, 0);
+  }
+  DecodeRun D;
+  uint32_t nw[32];
+#pragma unroll
+  for (int w = 0; w < 32; w++) nw[w] = 0;
+  if (!decode_run(in, in_size, cap, desc, local_off, tile_pre, G, R, S, err, stq, D, nw))
+    return;  // the frame's stream header is bad (k_scan_chain recorded it)
+  // ---- K6 on the run, as k_decode_idct's on its group, into the output
+  // frame's geometry: lane l's block is block jo0 + l of plane p of R
+  const int p = D.p;
+  xf::Unit U;
+  U.p = p;
+  U.cum = R.cum[p];
+  U.nb = R.cum[p + 1] - R.cum[p];
+  U.poff = p == 0 ? R.poff[0] : (p == 1 ? R.poff[1] : R.poff[2]);
+  U.pw = p == 0 ? R.pw[0] : (p == 1 ? R.pw[1] : R.pw[2]);
+  U.bw = p == 0 ? R.bw[0] : (p == 1 ? R.bw[1] : R.bw[2]);
+  U.bmag = p == 0 ? R.bmag[0] : (p == 1 ? R.bmag[1] : R.bmag[2]);
+  U.local0 = 0;
+  uint8_t* fr = frame + (size_t)D.f * R.fbytes;
+  uint32_t acc = nw[0] & 0xFFFF0000u;
+#pragma unroll
+  for (int w = 1; w < 32; w++) acc |= nw[w];
+  const bool isdc = D.live && acc == 0u;
+  if (isdc) {  // the DC-only constant block (see k_decode_idct)
+    constexpr float c0 = xf::c_dct[0];
+    const float z = (float)(int16_t)nw[0] * sq[0];  // dequantise (DCT.cpp:331)
+    const float u = 0.0f + c0 * z;                  // stage 1: the k = 0 term
+    float Sv = 0.0f + u * c0;                       // stage 2: the k = 0 term
+    Sv = __builtin_amdgcn_fmed3f(Sv, -128.0f, 127.0f);  // (as idct_rows, DCT.cpp:358-362)
+    uint32_t px = xf::bits(Sv + xf::kMagicPx);
+    if (__builtin_amdgcn_fractf(Sv) == 0.5f)
+      px = (uint32_t)((int)__builtin_truncf(Sv + __builtin_copysignf(xf::kHalfDown, Sv)) + 128);
+    const uint32_t v4 = (px & 0xFFu) * 0x01010101u;
+    const uint2 rowv = make_uint2(v4, v4);
+#pragma unroll
+    for (uint32_t r = 0; r < 8; r++)
+      *reinterpret_cast<uint2*>(fr + xf::block_row_offset(U, D.jo0 + lane, r)) = rowv;
+  }
+  const uint64_t rest = __ballot(D.live && !isdc);
+  const uint32_t nrest = (uint32_t)__popcll(rest);
+  const uint32_t rrank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rest >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rest, 0u));
+  if (D.live && !isdc) s_blk[rrank] = (uint16_t)lane;  // compacted position -> the block's lane in the run
+  float* tile = reinterpret_cast<float*>(stq);
+#pragma unroll 1
+  for (uint32_t base = 0; base < nrest;) {
+    const bool wide = nrest - base > 8u;
+    const uint32_t span = wide ? 16u : 8u, stride = wide ? (uint32_t)xf::kTile : (uint32_t)xf::kTile8;
+    const uint32_t s = rrank - base;
+    if (D.live && !isdc && rrank >= base && s < span) {
+      uint4* img = reinterpret_cast<uint4*>(tile + s * stride + (wide ? xf::img_word(s) : 0u));
+#pragma unroll
+      for (int c = 0; c < 8; c++) img[c] = make_uint4(nw[4 * c], nw[4 * c + 1], nw[4 * c + 2], nw[4 * c + 3]);
+    }
+    if (lane < span && base + lane >= nrest) {
+      uint4* img = reinterpret_cast<uint4*>(tile + lane * stride + (wide ? xf::img_word(lane) : 0u));
+#pragma unroll
+      for (int c = 0; c < 8; c++) img[c] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    xf::wave_sync();
+    if (wide) {
+      const uint32_t q = lane & 3u, b = lane >> 2;
+      uint2 w0, w1;
+      xf::idct_rows(tile + b * xf::kTile, q, b, sq, w0, w1);
+      if (base + b < nrest) {
+        const uint32_t off = xf::block_row_offset(U, D.jo0 + s_blk[base + b], 2u * q);
+        *reinterpret_cast<uint2*>(fr + off) = w0;
+        *reinterpret_cast<uint2*>(fr + off + U.pw) = w1;
+      }
+    } else {
+      const uint32_t r = lane & 7u, b = lane >> 3;
+      float qc[8];  // the lane's column of the plane's Q table, Q[k][r]
+#pragma unroll
+      for (int kk = 0; kk < 8; kk++) qc[kk] = sq[8 * kk + r];
+      const uint2 w = xf::idct_row8(tile + b * xf::kTile8, r, qc);
+      if (base + b < nrest)
+        *reinterpret_cast<uint2*>(fr + xf::block_row_offset(U, D.jo0 + s_blk[base + b], r)) = w;
+    }
+    xf::wave_sync();  // the next unit rewrites the tile
+    base += span;
+  }
 }
 
 }  // namespace myyuv_gpu

@@ -4,6 +4,7 @@
 // per-context workspace, and the launch sequences
 //   compress:   K1 fdct_quant -> K2 huff_encode (+ overflow pass) -> K4 stream_out
 //   decompress: parse -> scan -> K5 huff_decode -> K6 dequant_idct
+//   region:     parse -> scan -> decode_region (a rectangle's blocks only)
 // Every launch goes to one stream; nothing synchronises inside the
 // device-resident entry points, so frames pipeline back to back.
 // The context, the owners of its HIP resources and the entry points'
@@ -198,13 +199,34 @@ int set_qtables(myyuv_hip_ctx* c, const uint8_t q[3], hipStream_t s) {
 
 }  // namespace
 
+// What k_scan_chain writes for a batch of G.nframes frames and the decoders
+// read: the group offsets (4 B per block), the scan tiles' prefixes and
+// look-back status words, the stream descriptors, the error word.  All a
+// region decode needs (launch_decompress_region).
+static int reserve_scan(myyuv_hip_ctx* c, const FrameGeom& G) {
+  const uint32_t nf = G.nframes;
+  const uint32_t ntiles = ceil_div(G.cum[3], kScanTile);
+  int e = 0;
+  e |= c->loff.grow((size_t)G.cum[3] * nf * 4);
+  e |= c->tiles.grow((size_t)nf * (ntiles + 1) * 4);
+  e |= c->err.grow(8);
+  e |= c->desc.grow((size_t)nf * sizeof(StreamDesc));
+  const size_t st_bytes = (size_t)nf * (ntiles + 1) * 8;
+  if (c->status.n < st_bytes) {
+    e |= c->status.grow(st_bytes);
+    // zeroed before any kernel on any stream reads it
+    if (!e && (hipMemset(c->status.p, 0, st_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+      e |= MYYUV_E_HIP;
+  }
+  return e ? MYYUV_E_HIP : 0;
+}
+
 // Workspace for a batch of G.nframes frames (blocks numbered batch-globally;
 // scan tiles, stream descriptors and look-back status words per frame).
 int reserve(myyuv_hip_ctx* c, const FrameGeom& G) {
   const uint32_t nf = G.nframes;
   const uint32_t nblk = G.cum[3] * nf;
   const uint32_t nwaves = ceil_div(nblk, kWave);
-  const uint32_t ntiles = ceil_div(G.cum[3], kScanTile);
   int e = 0;
   e |= c->coef.grow((size_t)nwaves * kCoefQuadsPerWave * 16);  // natural-order quads
   e |= c->stage.grow((size_t)win_tiles_alloc(nf * G.tcum[3]) * kTileCap);
@@ -220,12 +242,9 @@ int reserve(myyuv_hip_ctx* c, const FrameGeom& G) {
     e |= c->zq.grow(256);
     if (!e && hipMemset(c->zq.p, 0, 256) != hipSuccess) e |= MYYUV_E_HIP;
   }
-  e |= c->loff.grow((size_t)nblk * 4);
-  e |= c->tiles.grow((size_t)nf * (ntiles + 1) * 4);
-  e |= c->err.grow(8);
+  e |= reserve_scan(c, G);
   e |= c->sink.grow((size_t)kSinkQuads * 16 * kSinkSlots);  // K1/K6: 2 x 64 quads + K1's 64 mask bytes + 64 words
   e |= c->psize.grow(4);
-  e |= c->desc.grow((size_t)nf * sizeof(StreamDesc));
   // [0], [1]: overflow counts, then K2's list and (single frames) the CAP-16 tier's (launch_overflow)
   e |= c->work.grow((size_t)nblk * (nf == 1 || MYYUV_R16_BATCH ? 8 : 4) + 256);
   {
@@ -235,13 +254,6 @@ int reserve(myyuv_hip_ctx* c, const FrameGeom& G) {
       if (!e && (hipMemset(c->fix.p, 0, kFixHeader * 4) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
         e |= MYYUV_E_HIP;
     }
-  }
-  const size_t st_bytes = (size_t)nf * (ntiles + 1) * 8;
-  if (c->status.n < st_bytes) {
-    e |= c->status.grow(st_bytes);
-    // zeroed before any kernel on any stream reads it
-    if (!e && (hipMemset(c->status.p, 0, st_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
-      e |= MYYUV_E_HIP;
   }
   return e ? MYYUV_E_HIP : 0;
 }
@@ -420,6 +432,50 @@ int launch_decompress(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_in,
   e |= launch(c, MYYUV_K_IDCT, k_dequant_idct, xf_grid(G, c->xf_resident[1]), dim3(256), s,
               c->coef.as<const uint4>(), c->rmask.as<const uint8_t>(), c->zq.as<const uint4>(), G, qt,
               static_cast<uint8_t*>(d_out), c->sink.as<uint4>());
+  return e ? MYYUV_E_HIP : 0;
+}
+
+// The region (rx, ry, rw, rh) of a w x h frame: multiples of 16 (whole blocks
+// in every plane, and the result a compressible frame), not empty, inside
+// the frame (sums in 64 bits).  R: the output frame's geometry, S: the
+// rectangle's place in the source planes and its segments.
+int make_region(uint32_t w, uint32_t h, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh, FrameGeom& R,
+                RegionSegs& S) {
+  if (((rx | ry | rw | rh) & 15u) || rw == 0 || rh == 0) return MYYUV_E_ARG;
+  if ((uint64_t)rx + rw > w || (uint64_t)ry + rh > h) return MYYUV_E_ARG;
+  if (make_geom(rw, rh, R)) return MYYUV_E_ARG;
+  S.scum[0] = 0;
+  for (int p = 0; p < 3; p++) {
+    const uint32_t sh = p ? 4 : 3;  // log2 of the plane's block size in luma pixels
+    S.bx[p] = rx >> sh;
+    S.by[p] = ry >> sh;
+    S.spr[p] = ceil_div(R.bw[p], kWave);
+    S.scum[p + 1] = S.scum[p] + S.spr[p] * (R.ph[p] / 8);
+  }
+  return 0;
+}
+
+// Region decode: payload f at d_in + f * cap -> the region's frame f at d_out +
+// f * R.fbytes.  The size table of the whole frame is scanned as
+// launch_decompress does; k_decode_region then reads the region's chunks
+// only, whatever MYYUV_DECODER says (there is no split form).
+int launch_decompress_region(myyuv_hip_ctx* c, const FrameGeom& G, const FrameGeom& R, const RegionSegs& S,
+                             const void* d_in, const uint32_t* d_size, uint32_t cap, void* d_out, hipStream_t s) {
+  const uint32_t nf = G.nframes;
+  const uint32_t ntiles = ceil_div(G.cum[3], kScanTile);
+  unsigned long long* err = c->err.as<unsigned long long>();
+  StreamDesc* desc = c->desc.as<StreamDesc>();
+  const uint8_t* in = static_cast<const uint8_t*>(d_in);
+  int e = 0;
+  ScanSrc SS;
+  for (int i = 0; i < 4; i++) SS.cum[i] = G.cum[i];
+  for (int p = 0; p < 3; p++) SS.pos[p] = 0;
+  e |= launch(c, MYYUV_K_SCAN, k_scan_chain, dim3(ntiles, nf), dim3(256), s, in, cap, SS, d_size, cap, G, desc,
+              c->loff.as<uint32_t>(), c->tiles.as<uint32_t>(), ntiles, c->status.as<unsigned long long>(),
+              next_epoch(c), err);
+  e |= launch(c, MYYUV_K_REGION, k_decode_region, dim3(S.scum[3], nf), dim3(kWave), s, in, d_size, cap,
+              (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, R, S,
+              c->qtd.as<const QTables>(), static_cast<uint8_t*>(d_out), err);
   return e ? MYYUV_E_HIP : 0;
 }
 
@@ -869,6 +925,112 @@ int myyuv_gpu_dct_decompress_to_bmp(myyuv_hip_handle c, const uint8_t* payload, 
     return MYYUV_E_HIP;
   if ((e = launch_decompress(c, G, c->payload.p, c->psize.as<const uint32_t>(), cap, c->frame.p, s)) ||
       (e = launch_to_bmp(c, c->frame.p, w, h, 1, orient, bit_count, chroma, c->bmp.p, s)))
+    return e;
+  if ((e = read_err(c, s, bad_block))) {
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  if (d2h(bmp_data, c->bmp.p, out_bytes, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+// ---- region decode (defined in myyuv_hip.h) --------------------------------
+namespace {
+
+// The host-buffer region calls' device part: the whole stream goes up (the
+// host cannot know the region's byte ranges), the region's frame is left in
+// the context's `frame` buffer.
+int region_to_frame(myyuv_hip_ctx* c, const uint8_t* payload, uint32_t size, const FrameGeom& G, const FrameGeom& R,
+                    const RegionSegs& S, const uint8_t q[3], hipStream_t s) {
+  int e;
+  const uint32_t cap = (size + 3) & ~3u;
+  if ((e = reserve_scan(c, G)) || (e = set_qtables(c, q, s))) return e;
+  if (c->frame.grow(R.fbytes) || c->payload.grow(cap)) return MYYUV_E_HIP;
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (hipMemsetAsync(static_cast<uint8_t*>(c->payload.p) + (cap - 4), 0, 4, s) != hipSuccess ||
+      h2d(c->payload.p, payload, size, s) ||
+      hipMemcpyAsync(c->psize.p, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  return launch_decompress_region(c, G, R, S, c->payload.p, c->psize.as<const uint32_t>(), cap, c->frame.p, s);
+}
+
+}  // namespace
+
+int myyuv_gpu_dct_decompress_region(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w,
+                                    uint32_t h, const uint8_t q[3], uint32_t rx, uint32_t ry, uint32_t rw,
+                                    uint32_t rh, uint8_t* iyuv, int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payload || !iyuv || !q) return MYYUV_E_ARG;
+  int e = check_q(q);
+  if (e) return e;
+  FrameGeom G, R;
+  RegionSegs S;
+  if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G)) ||
+      (e = make_region(w, h, rx, ry, rw, rh, R, S)))
+    return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  if ((e = region_to_frame(c, payload, size, G, R, S, q, s))) return e;
+  if ((e = read_err(c, s, bad_block))) {
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  if (d2h(iyuv, c->frame.p, R.fbytes, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+int myyuv_gpu_dct_decompress_region_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_sizes,
+                                           uint32_t cap, uint32_t nframes, uint32_t w, uint32_t h,
+                                           const uint8_t q[3], uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh,
+                                           void* d_iyuv, void* stream) {
+  if (!c || !d_payload || !d_sizes || !d_iyuv || !q) return MYYUV_E_ARG;
+  if (((uintptr_t)d_payload & 3) || ((uintptr_t)d_iyuv & 7) || (nframes > 1 && (cap & 3))) return MYYUV_E_ARG;
+  FrameGeom G, R;
+  RegionSegs S;
+  int e = check_q(q);
+  if (e || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes)) || (e = make_region(w, h, rx, ry, rw, rh, R, S)))
+    return e;
+  Entry en(c, stream);
+  // (as several launches past the kernels' 32-bit block numbers or the grid's 65,535 frames)
+  const uint32_t per = std::min(launch_frames(G, c->launch_blocks), 65535u);
+  FrameGeom GL = G;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve_scan(c, GL)) || (e = set_qtables(c, q, en.s)))
+    return e;
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GL.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
+    const uint8_t* pay = static_cast<const uint8_t*>(d_payload) + (size_t)f0 * cap;
+    uint8_t* fr = static_cast<uint8_t*>(d_iyuv) + (size_t)f0 * R.fbytes;
+    if ((e = launch_decompress_region(c, GL, R, S, pay, d_sizes + f0, cap, fr, en.s))) return e;
+  }
+  return 0;
+}
+
+int myyuv_gpu_dct_decompress_region_to_bmp(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, int32_t width,
+                                           int32_t height, const uint8_t q[3], uint32_t rx, uint32_t ry,
+                                           uint32_t rw, uint32_t rh, uint16_t bit_count, uint32_t chroma,
+                                           uint8_t* bmp_data, int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payload || !bmp_data || !q || !chroma_ok(chroma)) return MYYUV_E_ARG;
+  int e = check_q(q);
+  if (e) return e;
+  FrameGeom G, R;
+  RegionSegs S;
+  uint32_t w = 0, h = 0, orient = 0;
+  if ((e = host_parse_headers(payload, size)) || (e = bmp_check(width, height, bit_count, &w, &h, &orient)) ||
+      (e = make_geom(w, h, G)) || (e = make_region(w, h, rx, ry, rw, rh, R, S)))
+    return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const size_t out_bytes = (size_t)rw * rh * (bit_count / 8);
+  if (c->bmp.grow(out_bytes)) return MYYUV_E_HIP;
+  if ((e = region_to_frame(c, payload, size, G, R, S, q, s)) ||
+      (e = launch_to_bmp(c, c->frame.p, rw, rh, 1, orient, bit_count, chroma, c->bmp.p, s)))
     return e;
   if ((e = read_err(c, s, bad_block))) {
     (void)reset_err(c, s);

@@ -22,10 +22,10 @@ CHROMA_NEAREST, CHROMA_LINEAR = 0, 1  # MYYUV_CHROMA_*
 
 KERNELS = ["fdct_quant", "huff_encode", "scan_tiles", "stream_out", "encode_tile", "huff_decode",
            "dequant_idct", "huff_encode_wide", "huff_encode_r16", "huff_encode_wave", "bmp_to_iyuv",
-           "fdct_fix", "iyuv_to_bmp"]
+           "fdct_fix", "iyuv_to_bmp", "decode_region"]
 # ids: MYYUV_K_* of include/myyuv_hip.h, in KERNELS order (tests/test_cabi.py checks both)
 (K_FDCT, K_HUFF_ENC, K_SCAN, K_COMPACT, K_ENCODE_TILE, K_HUFF_DEC, K_IDCT, K_HUFF_WIDE,
- K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP) = range(len(KERNELS))
+ K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP, K_REGION) = range(len(KERNELS))
 
 # the exported symbols include/myyuv_hip.h declares (checked by the CPU tests)
 EXPORTS = [
@@ -38,6 +38,8 @@ EXPORTS = [
     "myyuv_gpu_dct_compress_batch", "myyuv_gpu_dct_compress_frames", "myyuv_gpu_dct_decompress_frames",
     "myyuv_gpu_dct_decompress_batch", "myyuv_gpu_iyuv_to_bmp", "myyuv_gpu_iyuv_to_bmp_device",
     "myyuv_gpu_dct_decompress_to_bmp", "myyuv_gpu_dct_decompress_to_bmp_frames",
+    "myyuv_gpu_dct_decompress_region", "myyuv_gpu_dct_decompress_region_device",
+    "myyuv_gpu_dct_decompress_region_to_bmp",
 ]
 
 _lib = None
@@ -121,7 +123,12 @@ def load():
     L.myyuv_gpu_dct_decompress_to_bmp.argtypes = [vp, u8p, u32, i32, i32, u8p, u16, u32, u8p, i64p]
     L.myyuv_gpu_dct_decompress_to_bmp_frames.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u32), u32, i32, i32,
                                                          u8p, u16, u32, ctypes.POINTER(vp), i64p]
-    L.myyuv_debug_tinfo_guard.argtypes = [vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
+    L.myyuv_gpu_dct_decompress_region.argtypes = [vp, u8p, u32, u32, u32, u8p, u32, u32, u32, u32, u8p, i64p]
+    L.myyuv_gpu_dct_decompress_region_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, u32, u32, u32, u32,
+                                                         vp, vp]
+    L.myyuv_gpu_dct_decompress_region_to_bmp.argtypes = [vp, u8p, u32, i32, i32, u8p, u32, u32, u32, u32, u16, u32,
+                                                         u8p, i64p]
+    L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_k2_constants.argtypes = [ctypes.POINTER(u32)]  # diagnostic
@@ -400,6 +407,55 @@ class Codec:
         if rc:
             raise CodecError(rc, bad.value)
         return [o[:ob].tobytes() for o in outs]
+
+    # -- region decode: region = (rx, ry, rw, rh) in luma pixels, multiples of 16
+    # (defined in include/myyuv_hip.h; only the region's chunks are read) --
+    def decompress_region(self, payload, w, h, q, region):
+        """DCTYUV payload -> the rw x rh IYUV frame cropped from the full
+        decode at (rx, ry), as bytes."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        n = int(region[2]) * int(region[3]) * 3 // 2
+        out = np.empty(max(1, n), np.uint8)
+        self.decompress_region_into(src, w, h, q, region, out)
+        return out[:n].tobytes()
+
+    def decompress_region_into(self, payload, w, h, q, region, out):
+        """decompress_region from / into the caller's C-contiguous uint8 arrays
+        (`out` at least rw*rh*3/2 bytes; untouched when the call fails)."""
+        src = _u8_array(payload, "payload")
+        dst = _u8_array(out, "out", writable=True)
+        rx, ry, rw, rh = (int(v) for v in region)
+        if dst.nbytes < rw * rh * 3 // 2:
+            raise ValueError("output smaller than rw*rh*3/2")
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_decompress_region(self._h, _u8(src), src.nbytes, w, h, _u8(_q(q)), rx, ry, rw, rh,
+                                                    _u8(dst), ctypes.byref(bad))
+        if rc:
+            raise CodecError(rc, bad.value)
+
+    def decompress_region_device(self, d_payload, d_sizes, cap, nframes, w, h, q, region, d_iyuv, stream=None):
+        """Device-resident batch: stream f at d_payload + f*cap -> region frame
+        f at d_iyuv + f*rw*rh*3/2; asynchronous, errors through sync_status."""
+        rx, ry, rw, rh = (int(v) for v in region)
+        rc = load().myyuv_gpu_dct_decompress_region_device(self._h, d_payload, d_sizes, cap, nframes, w, h,
+                                                           _u8(_q(q)), rx, ry, rw, rh, d_iyuv, stream)
+        if rc:
+            raise CodecError(rc)
+
+    def decompress_region_to_bmp(self, payload, width, height, q, region, bit_count=32, chroma=CHROMA_LINEAR):
+        """decompress_region, then iyuv_to_bmp of the region's frame on the
+        device (width / height signed: the orientation of the BMP written)."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        rx, ry, rw, rh = (int(v) for v in region)
+        n = rw * rh * (int(bit_count) // 8)
+        out = np.empty(max(1, n), np.uint8)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_decompress_region_to_bmp(self._h, _u8(src), src.size, int(width), int(height),
+                                                           _u8(_q(q)), rx, ry, rw, rh, int(bit_count), int(chroma),
+                                                           _u8(out), ctypes.byref(bad))
+        if rc:
+            raise CodecError(rc, bad.value)
+        return out[:n].tobytes()
 
     # -- device-resident API (pointers are device addresses, e.g. torch data_ptr) --
     def reserve(self, w, h):
