@@ -4,8 +4,10 @@
 // oracle.  argv[1]: "4" / "8" = build_r<CAP> + emit_chunk on every block;
 // "auto" = the kernel's class dispatch (block_class); "dense" = "auto" packed
 // the way k_huff_encode packs a tile (DenseWriter); "16" = build_r16 +
-// emit_chunk16 (the CAP-16 overflow tier, huff_r16.hpp).
-//   in:  u32 n, then n x 64 int16 coefficients in natural order
+// emit_chunk16 (the CAP-16 overflow tier, huff_r16.hpp); "single" = the
+// single-class marker's closed form against build_single_dc + emit_chunk
+// (check_single: no input).
+//   in: u32 n, then n x 64 int16 coefficients in natural order
 //   out: per block u8 ok, u8 size, then `size` chunk bytes (ok = 1);
 //        "dense": u32 run bytes, then the run
 #include <cstdio>
@@ -50,8 +52,48 @@ static bool build(const CoefRegs& R, const char* mode, EncState& S) {
   return cls == kClassR4 ? build_r<4>(R, msz, 64, S) : build_r<8>(R, msz, 64, S);
 }
 
+// "single": the K2 -> K4 marker of a single-class block (codec_common.hpp
+// single_chunk_words) against the encoder it stands for: for every 11-bit
+// key as a sign-extended DC coefficient, and for the all-zero block, the two
+// source words must be the 7 bytes emit_chunk(build_single_dc) writes, zeros
+// after.  Reads nothing; prints the number of cases checked.
+static int check_single() {
+  uint32_t checked = 0;
+  for (int c = -1; c < 2048; c++) {  // (-1: the all-zero block through build_single)
+    const int dc = c < 0 ? 0 : (c >= 1024 ? c - 2048 : c);
+    EncState S;
+    if (c < 0) {
+      CoefRegs R;
+      for (int w = 0; w < 32; w++) R.w[w] = 0u;
+      if (R.msz() != 0 || block_class(R, 0) != kClassSingle) return 4;
+      build_single(R, S);
+    } else {
+      build_single_dc(dc, S);
+    }
+    uint8_t want[8] = {0};
+    HostWriter hw{want};
+    emit_chunk(S, 1, hw);
+    hw.align_byte();
+    if (hw.pos != (int)kSingleChunk || S.size != kSingleChunk) return 3;
+    const uint32_t so = kSrcSingle | ((uint32_t)dc & 0x7FFu);
+    if (!src_is_single(so) || so == kSrcOverflow) return 5;
+    uint32_t w[2];
+    single_chunk_words(so, w[0], w[1]);
+    if (std::memcmp(w, want, 8) != 0) {
+      fprintf(stderr, "single: key %d: words %08x %08x\n", c, w[0], w[1]);
+      return 1;
+    }
+    checked++;
+  }
+  // a stage offset and the overflow mark are no markers
+  if (src_is_single(0u) || src_is_single(kWinTilesBig * kTileCap - 1u) || src_is_single(kSrcOverflow)) return 5;
+  printf("%u\n", checked);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   const char* mode = argc > 1 ? argv[1] : "auto";
+  if (mode[0] == 's') return check_single();
   uint32_t n = 0;
   if (fread(&n, 4, 1, stdin) != 1) return 2;
   std::vector<int16_t> c((size_t)n * 64);

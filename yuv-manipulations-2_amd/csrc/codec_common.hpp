@@ -271,19 +271,40 @@ __host__ __device__ __forceinline__ uint32_t win_first_tile(uint32_t T, uint32_t
 //   stage:  kTileCap bytes per batch tile (the window's tiles' regions are
 //           contiguous), one kWaveRun-byte region per 64-block run: the chunks
 //           of the run's blocks with at most 8 distinct symbols, back to back
-//           in the run's (class-sorted) order (a "dense run");
-//   srcoff: u32 per block: the chunk's byte offset from its window's first
-//           tile's stage region, kSrcOverflow for a block with more symbols,
+//           in the run's (class-sorted) order (a "dense run"); k_huff_encode
+//           puts no single-class block (msz <= 1) there;
+//   srcoff: u32 per block, one of three kinds: the chunk's byte offset from
+//           its window's first tile's stage region (below kWinTilesBig *
+//           kTileCap); kSrcOverflow for a block with more than 8 symbols,
 //           whose chunk the overflow passes write to oslots at g * kMaxChunk;
+//           kSrcSingle | key11 for a single-class block of k_huff_encode: no
+//           chunk is stored anywhere, its 7 bytes are a closed form of the
+//           DC's low 11 bits (single_chunk_words; k_encode_tile writes its
+//           single chunks to the stage with ordinary offsets);
 //   tinfo:  kTInfoWords u32 per tile: [0] overflow chunk bytes (the overflow
 //           passes add to it), [1 .. 4] the tile's dense-chunk bytes (k_huff_encode:
-//           all in [1]; k_encode_tile: per wave), [8] the tile's exclusive
-//           prefix in its frame's content (k_tile_scan).
+//           all in [1], the single-class blocks' 7 bytes each included;
+//           k_encode_tile: per wave), [8] the tile's exclusive prefix in its
+//           frame's content (k_tile_scan).
 constexpr uint32_t kTileCap = kK2Group * kMaxChunk;
 constexpr uint32_t kWaveRun = kWave * kMaxChunk;
 constexpr uint32_t kTInfoWords = 16;
 constexpr uint32_t kTInfoPrefix = 8;
 constexpr uint32_t kSrcOverflow = 0xFFFFFFFFu;
+constexpr uint32_t kSrcSingle = 0x80000000u;  // | the DC's low 11 bits
+constexpr uint32_t kSingleChunk = 7;          // bytes of a single-class block's chunk
+static_assert(kWinTilesBig * kTileCap <= kSrcSingle && (kSrcSingle | 0x7FFu) < kSrcOverflow,
+              "stage offsets, single markers and kSrcOverflow are told apart by value");
+__host__ __device__ __forceinline__ bool src_is_single(uint32_t so) { return (so & 0xFFFFF800u) == kSrcSingle; }
+// The chunk of a single-class block (build_single_dc + emit_chunk,
+// huff_common.hpp) as source words: bytes 01 00 03 00 | key & 0xFF | key >> 8 | 00
+// (u16 nbits = 1, u8 table_bytes = 3, group header 0, the 11-bit key, one code
+// byte), zeros after.  so: the block's srcoff marker (or any word with the key
+// in its low 11 bits).
+__host__ __device__ __forceinline__ void single_chunk_words(uint32_t so, uint32_t& w0, uint32_t& w1) {
+  w0 = 0x00030001u;
+  w1 = so & 0x7FFu;
+}
 // The hand-off is laid out for exactly four K2 waves per tile: k_tile_scan sums
 // tinfo words 1..4, k_stream_out keeps four run totals, k_encode_tile's
 // phase 1 covers 4 waves x 4 units x 16 blocks, and tinfo word kTInfoPrefix

@@ -973,7 +973,8 @@ namespace {
 // kWinTiles or kWinTilesBig, k2_win).  Sort slots are the (tile round, wave)
 // pairs that classified them, so the order is stable: class, then window slot
 // (tile, block).
-// sort keys: the single class, then each class K2 builds (r4, r8, r8x)
+// sort keys: key 0, the single class's, stays empty (those blocks are
+// finished at classification and take the dead key), then each class K2 builds (r4, r8, r8x)
 // split by message length (the per-position loops run to the run's longest
 // message), then the ovf class (built by the overflow passes: one key), the
 // dead slots last.  Length buckets (MYYUV_K2_MSZ_SPLIT): 2 -> <= 8, <= 16,
@@ -1051,7 +1052,6 @@ __device__ __forceinline__ uint32_t wave_incl_sum_full(uint32_t x) {
 template <uint32_t W>
 struct WinScratch {
   uint16_t slot[WinCfg<W>::kBlocks];  // sorted position -> window slot (tile << 8 | block)
-  uint16_t dc[WinCfg<W>::kBlocks];    // window slot -> its DC coefficient's low 11 bits (from K1's block word)
   uint8_t msz[WinCfg<W>::kBlocks], cls[WinCfg<W>::kBlocks], rm[WinCfg<W>::kBlocks];
   uint32_t cnt[WinCfg<W>::kScanVals];  // per (key, sort slot): count, then exclusive position
   uint32_t gb[W];             // batch-global index of tile k's block 0
@@ -1064,10 +1064,15 @@ struct WinScratch {
 // K2 over K1's coefficients in HBM: one workgroup per window of W (k2_win)
 // batch tiles (grid: windows).
 //   coef: natural-order quads (codec_common.hpp); sizes: [n] u8.
-// 1. classify: thread i takes block i of each of the window's tiles (one
-//    coefficient load per block, coalesced), its message length and class;
-// 2. a counting sort of the window's blocks by class (ballot ranks per round
-//    and wave, one wave scans the counts);
+// 1. classify: thread i takes block i of each of the window's tiles (K1's
+//    block word, 4 B per block, coalesced): its message length and class.  A
+//    single-class block (msz <= 1: half of a natural frame's) is finished
+//    here: sizes[g] = 7 and srcoff[g] = kSrcSingle | the DC's low 11 bits
+//    (coalesced stores), K4 forms the chunk from the marker
+//    (codec_common.hpp single_chunk_words), and its 7 bytes are added to the
+//    tile's total from a per-round ballot count;
+// 2. a counting sort of the window's other blocks by class (ballot ranks per
+//    round and wave, one wave scans the counts);
 // 3. the sorted blocks in 64-block runs, heaviest run first, taken by the
 //    waves from an LDS counter (no barrier between runs: a wave that drew
 //    light runs takes more of them).  Each lane builds its block's code, a
@@ -1075,11 +1080,12 @@ struct WinScratch {
 //    (DenseWriter), srcoff records where, and the run's chunk bytes are added
 //    to their tiles' totals in LDS; blocks with more than 8 distinct symbols
 //    go to the overflow worklist;
-// 4. the last wave to finish publishes the tiles' totals (tinfo word 1).
+// 4. the last wave to finish publishes the tiles' totals (tinfo word 1); a
+//    window of single-class blocks alone has no run and publishes all the same.
 // Sorting over 4 tiles rather than one makes the runs more uniform: per
 // 4032x3008 frame the waves' class mix (single / <= 4 / <= 8 / rest) drops
 // from 1859 / 834 / 740 / 1010 runs to 2220 / 968 / 652 / 603
-// (tools/k2_window_sim.py).
+// (tools/k2_window_sim.py, with the single-class blocks still in runs).
 #ifndef MYYUV_K2_WAVES
 #define MYYUV_K2_WAVES 5  // 5 workgroups of 4 waves per CU: <= 96 VGPRs (12 spilled; 6 measured +1.5 % before the emit tables, −1 % after: its spills grew; tools/ab_bench.sh, tools/kus_ab.sh)
 #endif
@@ -1134,6 +1140,7 @@ __global__ __launch_bounds__(kK2Group, MYYUV_K2_WAVES) void k_huff_encode(const 
   // 4 B per block, coalesced), with per-round ballot ranks
   uint32_t ent[W];  // per round: class | msz << 3 | row mask << 10 | rank << 18
   uint32_t biv[W];
+  uint32_t nsg[W];  // per round: the wave's single-class blocks (wave-uniform)
 #pragma unroll
   for (uint32_t k = 0; k < W; k++) biv[k] = tid < nlk[k] ? binfo[gbk[k] + tid] : 0u;
 #ifdef MYYUV_STAMPS
@@ -1143,10 +1150,19 @@ __global__ __launch_bounds__(kK2Group, MYYUV_K2_WAVES) void k_huff_encode(const 
 #pragma unroll
   for (uint32_t k = 0; k < W; k++) {
     const uint32_t bi = biv[k];
-    const uint32_t cls = tid < nlk[k] ? (bi >> 15) & 7u : kClassDead;
+    // a single-class block (msz <= 1) ends here: its chunk is a closed form
+    // of the DC's low 11 bits, which K4 rebuilds from the srcoff marker
+    // (single_chunk_words), so it takes the dead key: no sort slot, no run,
+    // no stage bytes.  Its 7 bytes join the tile's total after the barrier.
+    const bool sgl = tid < nlk[k] && ((bi >> 15) & 7u) == kClassSingle;
+    if (sgl) {
+      sizes[gbk[k] + tid] = (uint8_t)kSingleChunk;
+      srcoff[gbk[k] + tid] = kSrcSingle | ((bi >> 18) & 0x7FFu);
+    }
+    nsg[k] = (uint32_t)__popcll(__ballot(sgl));
+    const uint32_t cls = tid < nlk[k] && !sgl ? (bi >> 15) & 7u : kClassDead;
     const uint32_t m = (bi >> 8) & 127u, rm = bi & 0xFFu;
     const uint32_t key = sort_key(cls, m);
-    sc.dc[(k << 8) | tid] = (uint16_t)(bi >> 18);  // the DC's low 11 bits (build_single_dc uses those)
     // the round's count per key and the lane's rank among its key's lanes
     // from one ballot per key bit: a lane's equal-key mask is the AND of each
     // bit's ballot or its complement (lane order: a stable sort), lane c < kKeys
@@ -1170,6 +1186,14 @@ __global__ __launch_bounds__(kK2Group, MYYUV_K2_WAVES) void k_huff_encode(const 
   KWSTAMP(5);
 #endif
   __syncthreads();
+  // the single-class blocks' bytes into their tiles' totals (the barrier
+  // orders the zeroing of sc.tot): lane k adds the wave's count of round k
+  if (lane < W) {
+    uint32_t n = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++) n = lane == k ? nsg[k] : n;
+    if (n) atomicAdd(&sc.tot[lane], kSingleChunk * n);
+  }
   // ---- 2. exclusive scan of the counts in (key, round, wave) order (wave 0)
   if (wave == 0) {
     uint32_t v[kScanPer], sum = 0;
@@ -1225,9 +1249,9 @@ __global__ __launch_bounds__(kK2Group, MYYUV_K2_WAVES) void k_huff_encode(const 
     const bool bld = live && mc != kClassOvf;  // (ovf blocks: straight to the worklist)
     const uint32_t k = sl >> 8;
     const uint32_t mg = sc.gb[k] + (sl & 255u);
-    uint32_t wcls = kClassDead;  // the run's heaviest class to build
+    uint32_t wcls = kClassDead;  // the run's heaviest class to build (no single-class block is sorted)
 #pragma unroll
-    for (int c = kClassOvf - 1; c >= 0; c--)
+    for (int c = kClassOvf - 1; c > (int)kClassSingle; c--)
       if (wcls == kClassDead && __ballot(bld && mc == (uint32_t)c) != 0) wcls = (uint32_t)c;
     const int wmsz = max(wave_max_full(bld ? mm : 0), 1);
     EncState S;
@@ -1235,15 +1259,7 @@ __global__ __launch_bounds__(kK2Group, MYYUV_K2_WAVES) void k_huff_encode(const 
     // (the coefficients are loaded inside each class's branch: loaded before
     // it, they are spilled to scratch across the branch, one dependent load
     // round trip per quad)
-    if (wcls == kClassSingle) {
-      // one symbol: the DC coefficient (word 0 of quad 0), or 0
-      // (single-class runs take the DC from LDS, kept at classification, not from HBM)
-      const uint32_t dc = bld ? (uint32_t)sc.dc[sl] : 0u;
-      if (bld) {
-        build_single_dc((int)(int16_t)dc, S);
-        ok = true;
-      }
-    } else if (wcls == kClassR4) {
+    if (wcls == kClassR4) {
       CoefRegs R;
       R.load(coef, zq, bld ? mg : 0u, bld ? mrm : 0u);
       if (bld) ok = build_r<4>(R, mm, wmsz, S);

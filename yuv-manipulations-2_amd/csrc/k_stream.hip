@@ -299,6 +299,7 @@ __global__ __launch_bounds__(256) void k_tile_scan(uint32_t* __restrict__ tinfo,
 }
 
 // One tile: its chunks, in block order, from the K2 runs / overflow slots
+// (a single-class block's 7 bytes from its srcoff marker alone: no load)
 // straight into the stream, one lane per block.  Every stream dword inside a
 // plane's content is stored once, by the chunk owning its first byte, with
 // the next chunk's first bytes — at most 3, so always the next chunk's header
@@ -362,30 +363,43 @@ __global__ __launch_bounds__(256) void k_stream_out(const uint32_t* __restrict__
   if (surplus) return;
   const uint32_t sz = live ? sz0 : 0u;
   const uint32_t so = live ? so0 : 0u;
+  // a single-class block of k_huff_encode has no stored chunk: its srcoff
+  // is a marker (codec_common.hpp), never an address; the lane loads nothing
+  // and takes the chunk's two words from the marker after the round trip
+  const bool sg = src_is_single(so);
   const uint32_t* src;
   uint32_t sh;  // source byte misalignment
   if (so == kSrcOverflow) {
     src = oslots + (size_t)(gb + tid) * kSlotWords;
     sh = 0;
   } else {
-    src = stage + (size_t)win_first_tile(T, W) * (kTileCap / 4) + (so >> 2);  // (window-relative)
-    sh = so & 3u;
+    const uint32_t sso = sg ? 0u : so;
+    src = stage + (size_t)win_first_tile(T, W) * (kTileCap / 4) + (sso >> 2);  // (window-relative)
+    sh = sso & 3u;
   }
-  const uint32_t* s1 = plane_end ? stage
+  // the block after the tile: a marker's header is a constant (its two loads
+  // stay unconditional, at `stage`, as at a plane's end)
+  const bool sg1 = !plane_end && src_is_single(so1);
+  const uint32_t* s1 = plane_end || sg1 ? stage
                        : so1 == kSrcOverflow ? oslots + (size_t)(gb + nloc) * kSlotWords
                                              : stage + (size_t)win_first_tile(T + 1, W) * (kTileCap / 4) + (so1 >> 2);
-  const uint32_t r1 = plane_end || so1 == kSrcOverflow ? 0u : so1 & 3u;
+  const uint32_t r1 = plane_end || sg1 || so1 == kSrcOverflow ? 0u : so1 & 3u;
   // Round trip 2: the chunk's first kVw source words (every chunk of the
   // bench frame: its longest is 55 bytes; predicated per word: most chunks
   // are a few words, and unconditional loads measured slower), which also
   // give its header, and the next tile's first header
-  const uint32_t nsrc = (sh + sz + 3) >> 2;
+  const uint32_t nsrc = sg ? 0u : (sh + sz + 3) >> 2;
   const gu32* gsrc = (const gu32*)src;
   uint32_t v[kVw];
 #pragma unroll
   for (uint32_t k = 0; k < kVw; k++) v[k] = (k < nsrc) ? gsrc[k] : 0u;
   const uint32_t n0 = s1[0], n1 = s1[1];
-  const uint32_t nxh = plane_end ? 0u : (r1 ? (n0 >> (8 * r1)) | (n1 << (32 - 8 * r1)) : n0);
+  uint32_t sw0, sw1;
+  single_chunk_words(so, sw0, sw1);
+  v[0] = sg ? sw0 : v[0];
+  v[1] = sg ? sw1 : v[1];
+  single_chunk_words(so1, sw0, sw1);
+  const uint32_t nxh = plane_end ? 0u : sg1 ? sw0 : (r1 ? (n0 >> (8 * r1)) | (n1 << (32 - 8 * r1)) : n0);
   const uint32_t hdr = sh ? (v[0] >> (8 * sh)) | (v[1] << (32 - 8 * sh)) : v[0];
   // ---- offsets in the tile (block order), the next lane's header (the
   // whole workgroup is active here: DPP forms)

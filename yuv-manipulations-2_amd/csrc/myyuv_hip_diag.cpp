@@ -125,6 +125,12 @@ int huff_encode_blocks(myyuv_hip_ctx* c, const int16_t* coef_zz, uint32_t nblock
   for (uint32_t g = 0; g < ntotal; g++) {
     uint8_t* dst = chunks160 + (size_t)g * kMaxChunk;
     std::memset(dst, 0, kMaxChunk);
+    if (src_is_single(soff[g])) {  // no stored chunk: the marker's closed form
+      uint32_t w[2];
+      single_chunk_words(soff[g], w[0], w[1]);
+      std::memcpy(dst, w, std::min<uint32_t>(sizes[g], sizeof(w)));
+      continue;
+    }
     const uint8_t* src = soff[g] == kSrcOverflow
                              ? oslots.data() + (size_t)g * kMaxChunk
                              : stage.data() + (size_t)win_first_tile(tile_of_block(G, g), W) * kTileCap + soff[g];
