@@ -13,6 +13,19 @@
  * stdout: "units <n> exact <m> mismatches <k> outputs <o> blocks <b> fixblocks <f>"
  * (exact: units with a block over the bound; fixblocks: such blocks, which
  * k_fdct_fix recomputes — every other block is checked against the reference)
+ *
+ * --per-block: after that line, "maxratio <x>": the largest |t - fl(Y_ref / Q)|
+ * / (A * kb[row]) over every output of every block with A > 0 (the bound of
+ * fdct_bfly.h says < 1), t the fast path's quantised value; then one line per
+ * block: "<index> <ok> <row> <col> <dec> <t> <tie row> <tie col> <tie>": the
+ * deciding row (the arg max of fma(A, kb[i], max |e|) over the rows) and
+ * column (the arg max of |e| in that row), the float bits (hex) of that
+ * maximum and of the deciding output's t, and where the reference's
+ * fl(Y_ref / Q) comes nearest to a half-integer and how near (float bits of
+ * the distance).  --dec-window W / --tie-window W: only the blocks whose
+ * maximum lies within W of 0.5 / whose distance is at most W (searches).
+ * -DMYYUV_BFLY_MUTANT=n builds a deliberately wrong emulation (fdct_bfly.h);
+ * its mismatches do not fail the run.
  */
 #include <math.h>
 #include <stdint.h>
@@ -42,7 +55,7 @@ static const float Dm[64] = {
 using namespace myyuv_bfly;
 
 /* reference: T = D X, Y = T D^T, roundf(Y / Q) (DCT.cpp:232-254, 269-277) */
-static void ref_block(const uint8_t* px, const float* Q, int16_t* out) {
+static void ref_block(const uint8_t* px, const float* Q, int16_t* out, float* tq = nullptr) {
   float X[64], T[64], Y[64];
   for (int i = 0; i < 64; i++) X[i] = (float)((int)px[i] - 128);
   for (int i = 0; i < 8; i++)
@@ -58,9 +71,29 @@ static void ref_block(const uint8_t* px, const float* Q, int16_t* out) {
       Y[i * 8 + j] = s;
     }
   for (int i = 0; i < 64; i++) out[i] = (int16_t)roundf(Y[i] / Q[i]);
+  if (tq)
+    for (int i = 0; i < 64; i++) tq[i] = Y[i] / Q[i];
 }
 
-int main(void) {
+static uint32_t fbits(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return u;
+}
+
+int main(int argc, char** argv) {
+  int per_block = 0;
+  double dec_window = -1.0, tie_window = -1.0;
+  for (int i = 1; i < argc; i++) {
+    if (!strcmp(argv[i], "--per-block"))
+      per_block = 1;
+    else if (!strcmp(argv[i], "--dec-window") && i + 1 < argc)
+      dec_window = atof(argv[++i]);
+    else if (!strcmp(argv[i], "--tie-window") && i + 1 < argc)
+      tie_window = atof(argv[++i]);
+    else
+      return 2;
+  }
   uint32_t n;
   if (fread(&n, 4, 1, stdin) != 1) return 2;
   uint8_t* px = (uint8_t*)malloc((size_t)n * 65);
@@ -72,6 +105,14 @@ int main(void) {
     bfly_row_bounds(R[p], KB[p]);
   }
   long units = 0, exact = 0, mism = 0, outputs = 0, fixblocks = 0;
+  struct Line {
+    uint32_t index;
+    int ok, row, col, trow, tcol;
+    float dec, t, tie;
+  };
+  Line* lines = per_block ? (Line*)malloc((size_t)(n ? n : 1) * sizeof(Line)) : nullptr;
+  size_t nlines = 0;
+  double maxratio = 0.0;
   for (uint32_t u0 = 0; u0 < n; u0 += 16) {
     const uint32_t nb = n - u0 < 16 ? n - u0 : 16;
     int ok = 1;
@@ -80,9 +121,33 @@ int main(void) {
     for (uint32_t b = 0; b < nb; b++) {
       const uint8_t* blk = px + (size_t)(u0 + b) * 65;
       const int p = blk[64];
-      okb[b] = bfly_block(blk, R[p], KB[p], fast[b]);
+      BflyDetail d;
+      okb[b] = bfly_block(blk, R[p], KB[p], fast[b], per_block ? &d : nullptr);
       ok &= okb[b];
       fixblocks += !okb[b];
+      if (per_block) {
+        int16_t ref[64];
+        float tq[64];
+        ref_block(blk, Q[p], ref, tq);
+        Line L = {u0 + b, okb[b], d.row, d.col, 0, 0, d.dec, d.t[d.row * 8 + d.col], 1.0f};
+        for (int i = 0; i < 64; i++) {
+          const double fr = (double)tq[i] - floor((double)tq[i]);
+          const float dist = (float)fabs(fr - 0.5);
+          if (dist < L.tie) {
+            L.tie = dist;
+            L.trow = i / 8;
+            L.tcol = i % 8;
+          }
+          if (d.a > 0.0f) {
+            const double ratio = fabs((double)d.t[i] - (double)tq[i]) / ((double)d.a * (double)KB[p][i / 8]);
+            if (ratio > maxratio) maxratio = ratio;
+          }
+        }
+        const bool all = dec_window < 0.0 && tie_window < 0.0;
+        if (all || (dec_window >= 0.0 && fabs((double)d.dec - 0.5) <= dec_window) ||
+            (tie_window >= 0.0 && (double)L.tie <= tie_window))
+          lines[nlines++] = L;
+      }
     }
     units++;
     exact += !ok;
@@ -104,5 +169,11 @@ int main(void) {
   }
   printf("units %ld exact %ld mismatches %ld outputs %ld blocks %u fixblocks %ld\n", units, exact, mism, outputs, n,
          fixblocks);
-  return mism ? 1 : 0;
+  if (per_block) {
+    printf("maxratio %.9g\n", maxratio);
+    for (size_t i = 0; i < nlines; i++)
+      printf("%u %d %d %d %08x %08x %d %d %08x\n", lines[i].index, lines[i].ok, lines[i].row, lines[i].col,
+             fbits(lines[i].dec), fbits(lines[i].t), lines[i].trow, lines[i].tcol, fbits(lines[i].tie));
+  }
+  return mism && !MYYUV_BFLY_MUTANT ? 1 : 0;
 }

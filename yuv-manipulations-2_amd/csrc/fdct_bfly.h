@@ -6,7 +6,9 @@
 // (xform_common.hpp fdct_fast) and the host check tools/diag/
 // fdct_bfly_check.cpp (tests/test_numerics.py), which emulates the kernel's
 // arithmetic and compares every unit that passes the bound with the
-// reference transform.
+// reference transform.  That the device build computes what the emulation
+// computes is checked on the GPU by the blocks K1 lists
+// (tests/test_gpu_fdct_edges.py).
 //
 // The reference: T = D X (k-ascending sums of rounded products), Y = T D^T,
 // coefficient roundf(fl(Y / Q)) (DCT.cpp:232-254, 269-277).  The fast path:
@@ -42,13 +44,34 @@
 #define MYYUV_BF_HD static inline
 #endif
 
+// MYYUV_BFLY_MUTANT (host check only, tests/test_fdct_edges.py): a deliberately
+// wrong build of the arithmetic below, to show that the test inputs tell it
+// from the real one.  1: the FMA chains as separate multiplies and adds; 2:
+// kC4 replaced by kC0 (one ulp of the constant).  Off (0) in every other
+// build; never in device code.
+#ifndef MYYUV_BFLY_MUTANT
+#define MYYUV_BFLY_MUTANT 0
+#endif
+#if MYYUV_BFLY_MUTANT && defined(__HIPCC__)
+#error "MYYUV_BFLY_MUTANT is for the host check only"
+#endif
+#if MYYUV_BFLY_MUTANT == 1
+#define MYYUV_BF_FMA(a, b, c) ((a) * (b) + (c))
+#else
+#define MYYUV_BF_FMA(a, b, c) fmaf(a, b, c)
+#endif
+
 namespace myyuv_bfly {
 
 // N: row 0 = c0 (the literal row 0 exactly), row 4 = c4 (+ - - + + - - +),
 // rows 2 / 6 = (a, b, -b, -a, -a, -b, b, a) / (b, -a, a, -b, -b, a, -a, b),
 // odd rows antisymmetric (N[i][7 - m] = -N[i][m]); each value the midpoint of
 // the literal entries it stands for (fdct_bfly_derive.py)
+#if MYYUV_BFLY_MUTANT == 2
+constexpr float kC0 = 0.3535533845424652f, kC4 = kC0;
+#else
 constexpr float kC0 = 0.3535533845424652f, kC4 = 0.3535534143447876f;
+#endif
 constexpr float kA2 = 0.4619397521018982f, kB2 = 0.19134166836738586f;
 constexpr float kA6 = 0.4619397521018982f, kB6 = 0.19134169816970825f;
 constexpr float kO1[4] = {0.49039262533187866f, 0.41573476791381836f, 0.27778512239456177f, 0.09754513204097748f};
@@ -58,7 +81,7 @@ constexpr float kO7[4] = {0.09754543751478195f, -0.2777852416038513f, 0.41573470
 constexpr float kBflyK = 7.946e-7f;
 
 MYYUV_BF_HD float odd4(const float (&o)[4], float d0, float d1, float d2, float d3) {
-  return fmaf(o[3], d3, fmaf(o[2], d2, fmaf(o[1], d1, o[0] * d0)));
+  return MYYUV_BF_FMA(o[3], d3, MYYUV_BF_FMA(o[2], d2, MYYUV_BF_FMA(o[1], d1, o[0] * d0)));
 }
 
 // Column transform of one block column: p[m] = pixel of row m (0..255, as
@@ -69,8 +92,8 @@ MYYUV_BF_HD void bfly_cols(const float (&p)[8], float (&t)[8]) {
   const float ss0 = s0 + s3, ss1 = s1 + s2, ds0 = s0 - s3, ds1 = s1 - s2;
   t[0] = kC0 * ((ss0 + ss1) - 1024.0f);
   t[4] = kC4 * (ss0 - ss1);
-  t[2] = fmaf(kA2, ds0, kB2 * ds1);
-  t[6] = fmaf(kB6, ds0, -kA6 * ds1);
+  t[2] = MYYUV_BF_FMA(kA2, ds0, kB2 * ds1);
+  t[6] = MYYUV_BF_FMA(kB6, ds0, -kA6 * ds1);
   t[1] = odd4(kO1, d0, d1, d2, d3);
   t[3] = odd4(kO3, d0, d1, d2, d3);
   t[5] = odd4(kO5, d0, d1, d2, d3);
@@ -84,8 +107,8 @@ MYYUV_BF_HD void bfly_rows(const float (&x)[8], float (&y)[8]) {
   const float ss0 = s0 + s3, ss1 = s1 + s2, ds0 = s0 - s3, ds1 = s1 - s2;
   y[0] = kC0 * (ss0 + ss1);
   y[4] = kC4 * (ss0 - ss1);
-  y[2] = fmaf(kA2, ds0, kB2 * ds1);
-  y[6] = fmaf(kB6, ds0, -kA6 * ds1);
+  y[2] = MYYUV_BF_FMA(kA2, ds0, kB2 * ds1);
+  y[6] = MYYUV_BF_FMA(kB6, ds0, -kA6 * ds1);
   y[1] = odd4(kO1, d0, d1, d2, d3);
   y[3] = odd4(kO3, d0, d1, d2, d3);
   y[5] = odd4(kO5, d0, d1, d2, d3);
@@ -105,7 +128,15 @@ MYYUV_BF_HD void bfly_row_bounds(const float* r, float* kb) {
 #if !defined(__HIPCC__)
 // The kernel's arithmetic for one whole block (host check): coefficients in
 // natural order; returns 0 when some output is not provably the reference's.
-static inline int bfly_block(const unsigned char* px, const float* R, const float* kb, short* out) {
+// d (may be null): what decided, for the per-block listing of the check.
+struct BflyDetail {
+  int row, col;  // the row with the largest fma(A, kb[row], max |e|), the output with the largest |e| in it
+  float dec;     // that largest value (the block is unproven when dec >= 0.5)
+  float a;       // A
+  float t[64];   // every output's t = Y_f * fl(1 / Q)
+};
+static inline int bfly_block(const unsigned char* px, const float* R, const float* kb, short* out,
+                             BflyDetail* d = nullptr) {
   unsigned a = 0;
   for (int i = 0; i < 64; i++) a += px[i] > 128 ? px[i] - 128u : 128u - px[i];
   const float af = (float)a;
@@ -121,15 +152,25 @@ static inline int bfly_block(const unsigned char* px, const float* R, const floa
     float y[8];
     bfly_rows(T[i], y);
     float em = 0.0f;
+    int vm = 0;
     for (int v = 0; v < 8; v++) {
       const float t = y[v] * R[i * 8 + v];
       const float uu = t + 0x1.8p23f;
       const float e = t - (uu - 0x1.8p23f);
+      if (fabsf(e) > em) vm = v;
       em = fmaxf(em, fabsf(e));
       out[i * 8 + v] = (short)(int)(uu - 0x1.8p23f);
+      if (d) d->t[i * 8 + v] = t;
     }
-    if (fmaf(af, kb[i], em) >= 0.5f) ok = 0;  // (the kernel: one fma, max over the rows)
+    const float dec = fmaf(af, kb[i], em);
+    if (dec >= 0.5f) ok = 0;  // (the kernel: one fma, max over the rows)
+    if (d && (i == 0 || dec > d->dec)) {
+      d->row = i;
+      d->col = vm;
+      d->dec = dec;
+    }
   }
+  if (d) d->a = af;
   return ok;
 }
 #endif

@@ -139,6 +139,64 @@ int huff_encode_blocks(myyuv_hip_ctx* c, const int16_t* coef_zz, uint32_t nblock
   return 0;
 }
 
+// K1 and its exact path (launch_fdct) over nblocks pixel blocks of one plane
+// (block_geom), one Q table; the coefficients in zig-zag order.  listed /
+// counts (may both be null): the launch's fix lists as K1 left them (its
+// parity's counts; k_fdct_fix zeroes only the other parity's), read after
+// the stream is synchronised.  listed[g] = 1 for each entry ua * 16 + b,
+// counts[0] the number of entries, counts[1] the longest list.  An entry past
+// the blocks, in another list than ua % kFixLists or listed twice, or a count
+// above fix_list_cap, is kDiagFixList.
+constexpr int kDiagFixList = 101;  // (diagnostic only: not a MYYUV_E_* code of include/myyuv_hip.h)
+int fdct_blocks(myyuv_hip_ctx* c, const uint8_t* px, uint32_t nblocks, const float qtable[64], int16_t* coef_zz,
+                uint8_t* listed, uint32_t counts[2]) {
+  if (!c || !px || !qtable || !coef_zz || nblocks == 0) return MYYUV_E_ARG;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const FrameGeom G = block_geom(nblocks);
+  QTables t;
+  std::memset(&t, 0, sizeof(t));
+  std::memcpy(t.q[0], qtable, 256);
+  finish_qtables(t, 1);
+  if (reserve(c, G) || c->frame.grow((size_t)nblocks * 64) || c->qtd.grow(sizeof(QTables)))
+    return MYYUV_E_HIP;
+  c->q_valid = false;
+  if (hipStreamSynchronize(s) != hipSuccess ||
+      hipMemcpy(c->qtd.p, &t, sizeof(t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(c->frame.p, px, (size_t)nblocks * 64, hipMemcpyHostToDevice) != hipSuccess)
+    return MYYUV_E_HIP;
+  const uint32_t par = c->fix_par;  // (launch_fdct uses it and flips it)
+  if (launch_fdct(c, G, c->frame.as<const uint8_t>(), c->qtd.as<const QTables>(), nullptr, s))
+    return MYYUV_E_HIP;
+  if (hipGetLastError() != hipSuccess || read_coef(c, nblocks, coef_zz)) return MYYUV_E_HIP;
+  for (uint32_t g = 0; g < nblocks; g++) {  // natural -> zigzag order
+    int16_t nat[64];
+    std::memcpy(nat, coef_zz + (size_t)g * 64, sizeof(nat));
+    for (int z = 0; z < 64; z++) coef_zz[(size_t)g * 64 + z] = nat[kZigzag[z]];
+  }
+  if (!listed) return 0;
+  const uint32_t units = G.ucum[3] * G.nframes, cap = fix_list_cap(units);
+  std::vector<uint32_t> fix(fix_words(units));
+  if (fix.size() * 4 > c->fix.n ||  // (read_coef synchronised the stream)
+      hipMemcpy(fix.data(), c->fix.p, fix.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return MYYUV_E_HIP;
+  std::memset(listed, 0, nblocks);
+  counts[0] = counts[1] = 0;
+  for (uint32_t l = 0; l < kFixLists; l++) {
+    const uint32_t n = *fix_count(fix.data(), par, l);
+    if (n > cap) return kDiagFixList;
+    counts[0] += n;
+    counts[1] = std::max(counts[1], n);
+    const uint32_t* list = fix_list(fix.data(), G, l);
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t g = list[i];  // ua * 16 + b; one plane: the block's index
+      if (g >= nblocks || g / kXfUnit % kFixLists != l || listed[g]) return kDiagFixList;
+      listed[g] = 1;
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -208,30 +266,17 @@ int myyuv_debug_tinfo_guard(myyuv_hip_handle c, uint32_t ntiles, int arm, uint32
 // ---- block-level KAT entry points -----------------------------------------
 int myyuv_gpu_fdct_blocks(myyuv_hip_handle c, const uint8_t* px, uint32_t nblocks,
                           const float qtable[64], int16_t* coef_zz) {
-  if (!c || !px || !qtable || !coef_zz || nblocks == 0) return MYYUV_E_ARG;
-  Entry en(c);
-  hipStream_t s = en.s;
-  const FrameGeom G = block_geom(nblocks);
-  QTables t;
-  std::memset(&t, 0, sizeof(t));
-  std::memcpy(t.q[0], qtable, 256);
-  finish_qtables(t, 1);
-  if (reserve(c, G) || c->frame.grow((size_t)nblocks * 64) || c->qtd.grow(sizeof(QTables)))
-    return MYYUV_E_HIP;
-  c->q_valid = false;
-  if (hipStreamSynchronize(s) != hipSuccess ||
-      hipMemcpy(c->qtd.p, &t, sizeof(t), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->frame.p, px, (size_t)nblocks * 64, hipMemcpyHostToDevice) != hipSuccess)
-    return MYYUV_E_HIP;
-  if (launch_fdct(c, G, c->frame.as<const uint8_t>(), c->qtd.as<const QTables>(), nullptr, s))
-    return MYYUV_E_HIP;
-  if (hipGetLastError() != hipSuccess || read_coef(c, nblocks, coef_zz)) return MYYUV_E_HIP;
-  for (uint32_t g = 0; g < nblocks; g++) {  // natural -> zigzag order
-    int16_t nat[64];
-    std::memcpy(nat, coef_zz + (size_t)g * 64, sizeof(nat));
-    for (int z = 0; z < 64; z++) coef_zz[(size_t)g * 64 + z] = nat[kZigzag[z]];
-  }
-  return 0;
+  return fdct_blocks(c, px, nblocks, qtable, coef_zz, nullptr, nullptr);
+}
+
+// Diagnostic: myyuv_gpu_fdct_blocks, and which blocks K1 listed for its exact
+// path: listed[g] = 1 for each entry of the launch's lists, counts[0] the
+// number of entries, counts[1] the longest list (fdct_blocks above).
+// 101 (kDiagFixList) when the lists are not what K1 may write.
+int myyuv_debug_fdct_blocks(myyuv_hip_handle c, const uint8_t* px, uint32_t nblocks, const float qtable[64],
+                            int16_t* coef_zz, uint8_t* listed, uint32_t counts[2]) {
+  if (!listed || !counts) return MYYUV_E_ARG;
+  return fdct_blocks(c, px, nblocks, qtable, coef_zz, listed, counts);
 }
 
 int myyuv_gpu_huff_encode_blocks(myyuv_hip_handle c, const int16_t* coef_zz, uint32_t nblocks,

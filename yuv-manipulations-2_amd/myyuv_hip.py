@@ -132,6 +132,8 @@ def load():
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_k2_constants.argtypes = [ctypes.POINTER(u32)]  # diagnostic
+    L.myyuv_debug_fdct_blocks.argtypes = [vp, u8p, u32, ctypes.POINTER(ctypes.c_float),
+                                          ctypes.POINTER(ctypes.c_int16), u8p, ctypes.POINTER(u32)]  # diagnostic
     _lib = L
     return L
 
@@ -538,6 +540,27 @@ class Codec:
         if rc:
             raise CodecError(rc)
         return out
+
+    def fdct_blocks_listed(self, px, qtable):
+        """Diagnostic (not in include/myyuv_hip.h): fdct_blocks, and which
+        blocks K1 listed for its exact path k_fdct_fix: (coef int16[n, 64]
+        zig-zag, listed bool[n], (the number of list entries, the longest of
+        the 32 lists)).  RuntimeError when the lists hold what K1 may not
+        write (an entry out of range or in the wrong list, a block twice, a
+        count above the list's capacity)."""
+        px = np.ascontiguousarray(px, np.uint8).reshape(-1, 64)
+        qt = np.ascontiguousarray(qtable, np.float32).reshape(64)
+        out = np.empty((px.shape[0], 64), np.int16)
+        listed = np.zeros(px.shape[0], np.uint8)
+        counts = (ctypes.c_uint32 * 2)()
+        rc = load().myyuv_debug_fdct_blocks(self._h, _u8(px), px.shape[0],
+                                            qt.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), _u8(listed), counts)
+        if rc == 101:  # kDiagFixList (myyuv_hip_diag.cpp)
+            raise RuntimeError("K1's fix lists are inconsistent")
+        if rc:
+            raise CodecError(rc)
+        return out, listed.astype(bool), (int(counts[0]), int(counts[1]))
 
     def huff_encode_blocks(self, coef_zz):
         c = np.ascontiguousarray(coef_zz, np.int16).reshape(-1, 64)
