@@ -17,6 +17,11 @@
 // input is cropped on the host):
 //   myyuv_cli in.myyuv -decompress -crop X Y W H -o out.myyuv
 //   myyuv_cli in.myyuv -to_bmp [24|32] [-chroma nearest|linear] -crop X Y W H -o out.bmp
+// a 1/2, 1/4 or 1/8-size frame of a compressed input (scaled decode,
+// include/myyuv_hip.h: the N x N inverse DCT of every block's low-frequency
+// corner, on the GPU; not combined with -crop):
+//   myyuv_cli in.myyuv -decompress -scale 1/2|1/4|1/8 -o out.myyuv
+//   myyuv_cli in.myyuv -to_bmp [24|32] [-chroma nearest|linear] -scale 1/2|1/4|1/8 -o out.bmp
 // and, beyond the reference CLI, many frames per invocation (SURVEY.md §8f
 // row 2; frames of one geometry share batched kernel launches):
 //   myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IN.myyuv...
@@ -52,6 +57,9 @@ void usage() {
             << "  myyuv_cli IMAGE.myyuv -decompress [-crop X Y W H] -o OUT.myyuv\n"
             << "  myyuv_cli IMAGE.myyuv -to_bmp [24|32] [-chroma nearest|linear] [-crop X Y W H] -o OUT.bmp\n"
             << "      (-crop: only that region, luma pixels from the top-left, multiples of 16)\n"
+            << "  myyuv_cli IMAGE.myyuv -decompress -scale 1/2|1/4|1/8 -o OUT.myyuv\n"
+            << "  myyuv_cli IMAGE.myyuv -to_bmp [24|32] [-chroma nearest|linear] -scale 1/2|1/4|1/8 -o OUT.bmp\n"
+            << "      (-scale: a compressed image at that size, straight from its DCT coefficients)\n"
             << "  myyuv_cli IMAGE.bmp -info\n"
             << "  myyuv_cli IMAGE.bmp -to_yuv IYUV -o OUT.myyuv\n"
             << "  myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IMAGE.myyuv...\n"
@@ -77,6 +85,35 @@ bool parse_crop(const std::vector<std::string>& args, size_t& a, uint32_t r[4]) 
   return true;
 }
 
+constexpr const char* kScaleHelp = "Invalid argument, -scale must be followed by `1/2`, `1/4` or `1/8`\n";
+constexpr const char* kScaleCropHelp = "Invalid arguments, -scale and -crop cannot be combined\n";
+constexpr const char* kScaleRawHelp = "Nothing to scale, image is not compressed (-scale needs DCT coefficients)\n";
+
+// `-scale 1/N` among the options of the command at args[a] (before `-o`):
+// taken out of args, N into denom (0: no -scale).  Returns a message to
+// print before the usage (exit 1), or nullptr.
+const char* take_scale(std::vector<std::string>& args, size_t a, uint32_t& denom) {
+  denom = 0;
+  size_t k = a + 1;
+  bool crop = false;
+  for (; k < args.size() && args[k] != "-o" && args[k] != "-scale"; k++) crop = crop || args[k] == "-crop";
+  if (k >= args.size() || args[k] != "-scale") return nullptr;
+  if (k + 1 >= args.size()) return kScaleHelp;
+  const std::string& v = args[k + 1];
+  if (v == "1/2")
+    denom = 2;
+  else if (v == "1/4")
+    denom = 4;
+  else if (v == "1/8")
+    denom = 8;
+  else
+    return kScaleHelp;
+  for (size_t j = k + 2; j < args.size() && args[j] != "-o"; j++) crop = crop || args[j] == "-crop";
+  if (crop) return kScaleCropHelp;
+  args.erase(args.begin() + k, args.begin() + k + 2);
+  return nullptr;
+}
+
 myyuv::YUV compress_dct(const myyuv::YUV& yuv, const std::vector<std::string>& params) {
   if (params.size() > 3)
     throw std::runtime_error("Error. Too many compression parameters. Can't be more than 3 parameters.");
@@ -91,8 +128,21 @@ myyuv::YUV compress_dct(const myyuv::YUV& yuv, const std::vector<std::string>& p
   return yuv.compress(myyuv::YUV::Compressions::DCT, q, 3);
 }
 
-int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& args) {
-  const std::string& cmd = args[a];
+int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& args_in) {
+  std::vector<std::string> args = args_in;
+  const std::string cmd = args[a];
+  uint32_t denom = 0;  // -scale 1/denom (0: none), taken out of args
+  if (cmd == "-decompress" || cmd == "-to_bmp") {
+    if (const char* msg = take_scale(args, a, denom)) {
+      std::cout << msg;
+      usage();
+      return 1;
+    }
+    if (denom && !yuv.isCompressed()) {
+      std::cout << kScaleRawHelp;
+      return 1;
+    }
+  }
   if (cmd == "-info") {
     const auto& h = yuv.header;
     std::cout << "Type: " << h.type[0] << h.type[1] << '\n'
@@ -158,14 +208,18 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     }
     myyuv::YUV out;
     const float ms = elapsed_ms([&] {
-      if (!crop)
+      if (denom)
+        out = myyuvDCT::decompress_DCT_planar_scaled(yuv, denom);
+      else if (!crop)
         out = yuv.decompress();
       else if (yuv.isCompressed())
         out = myyuvDCT::decompress_DCT_planar_region(yuv, r[0], r[1], r[2], r[3]);
       else
         out = myyuv::crop_region(yuv, r[0], r[1], r[2], r[3]);
     });
-    if (crop)
+    if (denom)
+      std::cout << "YUV DCT scaled decompression (1/" << denom << ") : " << ms << " ms\n";
+    else if (crop)
       std::cout << "YUV crop (" << r[0] << " " << r[1] << " " << r[2] << " " << r[3] << ") : " << ms << " ms\n";
     else
       std::cout << "YUV DCT decompression : " << ms << " ms\n";
@@ -209,9 +263,12 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     }
     myyuv::BMP out;
     const float ms = elapsed_ms([&] {
-      out = crop ? myyuv::yuv_to_bmp(yuv, r[0], r[1], r[2], r[3], bits, chroma) : myyuv::yuv_to_bmp(yuv, bits, chroma);
+      out = denom  ? myyuv::yuv_to_bmp_scaled(yuv, denom, bits, chroma)
+            : crop ? myyuv::yuv_to_bmp(yuv, r[0], r[1], r[2], r[3], bits, chroma)
+                   : myyuv::yuv_to_bmp(yuv, bits, chroma);
     });
-    std::cout << "YUV to BMP (" << bits << " " << mode << ") : " << ms << " ms\n";
+    std::cout << "YUV to BMP (" << bits << " " << mode << (denom ? " 1/" + std::to_string(denom) : std::string())
+              << ") : " << ms << " ms\n";
     out.dump(args[a + 1]);
     return 0;
   }

@@ -318,16 +318,23 @@ YUVHeader region_header(const YUVHeader& in, uint32_t rw, uint32_t rh) {
   return h;
 }
 
-// yuv_to_bmp of the whole frame (region == nullptr) or of region[0..3] = (rx, ry, rw, rh).
-BMP to_bmp(const YUV& yuv, const uint32_t* region, uint16_t bit_count, uint32_t chroma) {
+// yuv_to_bmp of the whole frame (region == nullptr, denom == 0), of
+// region[0..3] = (rx, ry, rw, rh), or of the compressed frame's scaled decode
+// (denom 2, 4 or 8; no region).
+BMP to_bmp(const YUV& yuv, const uint32_t* region, uint32_t denom, uint16_t bit_count, uint32_t chroma) {
   static_assert(MYYUV_CHROMA_LINEAR == 1, "the header's default chroma mode");
   if (!yuv.isValid()) throw std::runtime_error("YUV is invalid");
   if (yuv.getFourccFormat() != YUV::FourccFormats::IYUV) throw std::runtime_error("Incorrect format");
   if (bit_count != 24 && bit_count != 32) fail(MYYUV_E_BMP_UNSUPPORTED);
   const uint32_t fw = yuv.header.width, fh = yuv.header.height;
+  if (denom) {
+    if (yuv.getCompression() == YUV::Compressions::NONE)
+      throw std::runtime_error("Error. The image is not compressed: a scaled decode needs DCT coefficients");
+    if (denom != 2 && denom != 4 && denom != 8) fail(MYYUV_E_ARG);  // (the result's size depends on it)
+  }
   if (region && yuv.getCompression() == YUV::Compressions::NONE) check_region(fw, fh, region[0], region[1], region[2], region[3]);
   // (a compressed frame's region is checked by the C ABI, after the stream's header)
-  const uint32_t w = region ? region[2] : fw, h = region ? region[3] : fh;
+  const uint32_t w = region ? region[2] : (denom ? fw / denom : fw), h = region ? region[3] : (denom ? fh / denom : fh);
   // BMP::imageSize(), file_size and dump() hold the pixel array's size in 32
   // bits, and imageSize() forms w * h * bit_count before it divides: an image
   // past that cannot be a BMP (and a wrapped size would under-allocate `data`)
@@ -359,7 +366,10 @@ BMP to_bmp(const YUV& yuv, const uint32_t* region, uint16_t bit_count, uint32_t 
       throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
     int64_t bad = -1;
     if (fw > 0x7FFFFFFFu || fh > 0x7FFFFFFFu) fail(MYYUV_E_ARG);
-    rc = region ? myyuv_gpu_dct_decompress_region_to_bmp(t_codec.get(), yuv.data, yuv.header.data_size, (int32_t)fw,
+    rc = denom  ? myyuv_gpu_dct_decompress_scaled_to_bmp(t_codec.get(), yuv.data, yuv.header.data_size, (int32_t)fw,
+                                                         (int32_t)fh, yuv.compression_params, denom, bit_count,
+                                                         chroma, res.data, &bad)
+         : region ? myyuv_gpu_dct_decompress_region_to_bmp(t_codec.get(), yuv.data, yuv.header.data_size, (int32_t)fw,
                                                          (int32_t)fh, yuv.compression_params, region[0], region[1],
                                                          region[2], region[3], bit_count, chroma, res.data, &bad)
                 : myyuv_gpu_dct_decompress_to_bmp(t_codec.get(), yuv.data, yuv.header.data_size, bh.width, bh.height,
@@ -373,12 +383,17 @@ BMP to_bmp(const YUV& yuv, const uint32_t* region, uint16_t bit_count, uint32_t 
 
 }  // namespace
 
-BMP yuv_to_bmp(const YUV& yuv, uint16_t bit_count, uint32_t chroma) { return to_bmp(yuv, nullptr, bit_count, chroma); }
+BMP yuv_to_bmp(const YUV& yuv, uint16_t bit_count, uint32_t chroma) { return to_bmp(yuv, nullptr, 0, bit_count, chroma); }
+
+BMP yuv_to_bmp_scaled(const YUV& yuv, uint32_t denom, uint16_t bit_count, uint32_t chroma) {
+  if (denom == 0) fail(MYYUV_E_ARG);
+  return to_bmp(yuv, nullptr, denom, bit_count, chroma);
+}
 
 BMP yuv_to_bmp(const YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh, uint16_t bit_count,
                uint32_t chroma) {
   const uint32_t region[4] = {rx, ry, rw, rh};
-  return to_bmp(yuv, region, bit_count, chroma);
+  return to_bmp(yuv, region, 0, bit_count, chroma);
 }
 
 YUV crop_region(const YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh) {
@@ -598,6 +613,31 @@ myyuv::YUV decompress_DCT_planar_region(const myyuv::YUV& yuv, uint32_t rx, uint
   return res;
 }
 
+// The scaled decode of a compressed frame (include/myyuv_hip.h): the checks of
+// decompress_DCT_planar_region and its header rewrite with the scaled size.
+// A denom other than 2, 4 or 8 is refused here (the result's size depends on
+// it); the C ABI checks everything else.
+myyuv::YUV decompress_DCT_planar_scaled(const myyuv::YUV& yuv, uint32_t denom) {
+  using myyuv::YUV;
+  if (yuv.getFormatGroup() != YUV::FormatGroup::PLANAR)
+    throw std::runtime_error("Error decompressing: YUV must be planar");
+  if (yuv.getCompression() != YUV::Compressions::DCT)
+    throw std::runtime_error("Error this decompression is unimplemented");
+  if (yuv.header.compression_params_size != 3 || !yuv.compression_params)
+    throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
+  for (int p = 0; p < 3; p++)
+    if (yuv.compression_params[p] < 1 || yuv.compression_params[p] > 100)
+      throw std::runtime_error("Level of quality must be between 1 and 100");
+  if (denom != 2 && denom != 4 && denom != 8) fail(MYYUV_E_ARG);
+  YUV res;
+  res.header = myyuv::region_header(yuv.header, yuv.header.width / denom, yuv.header.height / denom);
+  res.data = new uint8_t[res.header.data_size ? res.header.data_size : 1];
+  int64_t bad = -1;
+  const int rc = myyuv_gpu_dct_decompress_scaled(t_codec.get(), yuv.data, yuv.header.data_size, yuv.header.width,
+                                                 yuv.header.height, yuv.compression_params, denom, res.data, &bad);
+  if (rc) fail(rc);
+  return res;
+}
 
 // Many compressed frames per call. Each frame is checked as YUV::decompress
 // -> decompress_map[DCT][IYUV] -> decompress_DCT_planar would, in input order

@@ -114,6 +114,12 @@ BMP yuv_to_bmp(const YUV& yuv, uint16_t bit_count = 32, uint32_t chroma = 1 /* M
 // (only the region is decoded), an uncompressed one is cropped on the host.
 BMP yuv_to_bmp(const YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh, uint16_t bit_count = 32,
                uint32_t chroma = 1 /* MYYUV_CHROMA_LINEAR */);
+// The same for the scaled decode of a DCT-compressed frame (denom 2, 4 or 8:
+// include/myyuv_hip.h, scaled decode): a (width/denom) x (height/denom) BMP
+// through myyuv_gpu_dct_decompress_scaled_to_bmp.  An uncompressed frame is
+// refused (std::runtime_error): there are no coefficients to scale from.
+BMP yuv_to_bmp_scaled(const YUV& yuv, uint32_t denom, uint16_t bit_count = 32,
+                      uint32_t chroma = 1 /* MYYUV_CHROMA_LINEAR */);
 // The region of an UNCOMPRESSED planar frame, rows copied on the host: the
 // frame myyuvDCT::decompress_DCT_planar_region returns for the compressed
 // form of the same pixels (same constraints, same header, same bytes).
@@ -130,6 +136,10 @@ myyuv::YUV decompress_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t
 // bytes are the frame's compression parameters; the header is
 // decompress_DCT_planar's with width = rw, height = rh, data_size = rw*rh*3/2.
 myyuv::YUV decompress_DCT_planar_region(const myyuv::YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh);
+// Scaled decode (include/myyuv_hip.h): the (width/denom) x (height/denom)
+// frame, denom 2, 4 or 8, from the low-frequency corner of every block.
+// decompress_DCT_planar's checks; its header with the scaled size.
+myyuv::YUV decompress_DCT_planar_scaled(const myyuv::YUV& yuv, uint32_t denom);
 // Many frames per call: frames of one geometry share
 // one batched launch of every kernel; result i is compress_DCT_planar(*frames[i]).
 std::vector<myyuv::YUV> compress_DCT_planar_batch(const std::vector<const myyuv::YUV*>& frames,

@@ -32,6 +32,10 @@ __global__ void k_decode_idct(const uint8_t*, const uint32_t*, uint32_t, const S
 __global__ void k_decode_region(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
                                 const uint32_t*, FrameGeom, FrameGeom, RegionSegs, const QTables*, uint8_t*,
                                 unsigned long long*);
+template <int N>
+__global__ void k_decode_scaled(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
+                                const uint32_t*, FrameGeom, uint32_t, uint32_t, const QTables*, uint4*, uint8_t*,
+                                unsigned long long*);
 template <uint32_t W>
 __global__ void k_huff_encode(const uint4*, const uint32_t*, const uint4*, FrameGeom, uint32_t*, uint32_t*,
                               uint8_t*, uint32_t*, uint32_t*, uint32_t*);

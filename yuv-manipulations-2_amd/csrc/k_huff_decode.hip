@@ -34,6 +34,7 @@
 //   words (the de-zig-zag of Huffman.cpp:148-153 is free) and the block is
 //   written as 8 quads of the codec_common.hpp layout that K6 reads.
 #include "codec_common.hpp"
+#include "idct_scaled.h"
 #include "k_stream.hpp"
 #include "xform_common.hpp"
 
@@ -1051,5 +1052,109 @@ __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_region(const uint
     base += span;
   }
 }
+
+// ---- scaled decode --------------------------------------------------------
+//
+// k_decode_scaled<N>: the fused decoder at 1/denom size, N = 8 / denom in
+// {4, 2, 1} (include/myyuv_hip.h, "Scaled decode").  Grid and decode are
+// k_decode_idct's: one wave per 64-block group (blockIdx.x) of frame
+// blockIdx.y, decode_group unchanged, so the whole chunk is decoded and a
+// malformed one gives the full decode's code and block; a block with a table
+// that is not "regular" goes through the coefficient buffer as there.  Then
+// each lane transforms the N x N low-frequency corner of its own block from
+// its nw[] registers (idct_scaled.h: at most 16 coefficients, 128 products;
+// no transpose tile) and stores N rows of N bytes at block (by, bx) of the
+// plane's (bw N) x (bh N) image: a group's blocks are consecutive in a block
+// row, so consecutive lanes write adjacent bytes.  Every offset of a row is a
+// multiple of N bytes (plane offsets and widths are), so a row is one store of
+// N bytes.
+template <int N>
+__global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_scaled(const uint8_t* __restrict__ in,
+                                                     const uint32_t* __restrict__ in_size,
+                                                     uint32_t cap,
+                                                     const StreamDesc* __restrict__ desc,
+                                                     const uint32_t* __restrict__ local_off,
+                                                     const uint32_t* __restrict__ tile_pre,
+                                                     FrameGeom G, uint32_t tiles_p0,
+                                                     uint32_t tiles_p1, const QTables* __restrict__ qt,
+                                                     uint4* __restrict__ coef,
+                                                     uint8_t* __restrict__ frame,
+                                                     unsigned long long* __restrict__ err) {
+  static_assert(N == 1 || N == 2 || N == 4, "1/8, 1/4 or 1/2");
+  __shared__ uint4 stq[kStageQuads + 1 + kGposQuads];
+  __shared__ float sq[64];
+  const uint32_t lane = threadIdx.x;
+  if (lane == 0) stq[kStageQuads] = make_uint4(0u, 0u, 0u, 0u);  // (ordered by decode_group's barrier)
+  {
+    // the plane's Q table by LDS-DMA (landed by decode_group's final vmcnt wait)
+    const uint32_t t = blockIdx.x;
+    const int p = t >= tiles_p0 ? (t >= tiles_p0 + tiles_p1 ? 2 : 1) : 0;
+    __builtin_amdgcn_global_load_lds((const void*)&qt->q[p][lane], (__attribute__((address_space(3))) void*)sq, 4,
+                                     0, 0);
+  }
+  DecodeGroup D;
+  uint32_t nw[32];
+#pragma unroll
+  for (int w = 0; w < 32; w++) nw[w] = 0;
+  bool direct;
+  if (!decode_group(in, in_size, cap, desc, local_off, tile_pre, G, tiles_p0, tiles_p1, coef, err, stq, D, nw,
+                    direct))
+    return;  // the frame's stream header is bad (k_scan_chain recorded it)
+  if (!D.live) return;
+  // the corner's coefficients, natural order: coefficient 8 u + v is half
+  // v & 1 of word 4 u + (v >> 1).  decode_general wrote a `direct` block to
+  // coef: the corner's rows (quad u = row u) are read back.
+  int16_t z[N * N];
+  float q[N * N];
+#pragma unroll
+  for (int u = 0; u < N; u++) {
+    uint32_t w0 = nw[4 * u], w1 = nw[4 * u + 1];
+    if (direct) {
+      const uint4 v = coef[coef_quad(D.gbase + D.g, u)];
+      w0 = v.x;
+      w1 = v.y;
+    }
+#pragma unroll
+    for (int v = 0; v < N; v++) {
+      const uint32_t w = v < 2 ? w0 : w1;
+      z[u * N + v] = (int16_t)((v & 1) ? w >> 16 : w & 0xFFFFu);
+      q[u * N + v] = sq[8 * u + v];
+    }
+  }
+  uint8_t px[N * N];
+  myyuv_scaled::idct_scaled_block<N>(z, q, px);
+  // plane p of the scaled frame: offsets and sizes are the full frame's
+  // divided by denom^2 = 64 / N^2 (whole: W and H are multiples of 16)
+  const int p = D.p;
+  const uint32_t cum = p == 0 ? G.cum[0] : (p == 1 ? G.cum[1] : G.cum[2]);
+  const uint32_t poff = p == 0 ? G.poff[0] : (p == 1 ? G.poff[1] : G.poff[2]);
+  const uint32_t bw = p == 0 ? G.bw[0] : (p == 1 ? G.bw[1] : G.bw[2]);
+  const uint64_t bmag = p == 0 ? G.bmag[0] : (p == 1 ? G.bmag[1] : G.bmag[2]);
+  const uint32_t local = D.g - cum;
+  const uint32_t by = div_magic(local, bmag), bx = local - by * bw;
+  const uint32_t pwn = bw * N;
+  uint8_t* o = frame + (size_t)D.f * ((G.fbytes >> 6) * (N * N)) + (poff >> 6) * (N * N) + by * N * pwn + bx * N;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    if constexpr (N == 1) {
+      o[0] = px[0];
+    } else if constexpr (N == 2) {
+      *reinterpret_cast<uint16_t*>(o + i * pwn) = (uint16_t)(px[2 * i] | (px[2 * i + 1] << 8));
+    } else {
+      *reinterpret_cast<uint32_t*>(o + i * pwn) =
+          (uint32_t)px[4 * i] | ((uint32_t)px[4 * i + 1] << 8) | ((uint32_t)px[4 * i + 2] << 16) |
+          ((uint32_t)px[4 * i + 3] << 24);
+    }
+  }
+}
+template __global__ void k_decode_scaled<1>(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
+                                            const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t,
+                                            const QTables*, uint4*, uint8_t*, unsigned long long*);
+template __global__ void k_decode_scaled<2>(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
+                                            const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t,
+                                            const QTables*, uint4*, uint8_t*, unsigned long long*);
+template __global__ void k_decode_scaled<4>(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
+                                            const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t,
+                                            const QTables*, uint4*, uint8_t*, unsigned long long*);
 
 }  // namespace myyuv_gpu

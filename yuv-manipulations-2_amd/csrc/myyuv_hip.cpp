@@ -5,6 +5,7 @@
 //   compress:   K1 fdct_quant -> K2 huff_encode (+ overflow pass) -> K4 stream_out
 //   decompress: parse -> scan -> K5 huff_decode -> K6 dequant_idct
 //   region:     parse -> scan -> decode_region (a rectangle's blocks only)
+//   scaled:     parse -> scan -> decode_scaled (every block, at 1/2, 1/4 or 1/8 size)
 // Every launch goes to one stream; nothing synchronises inside the
 // device-resident entry points, so frames pipeline back to back.
 // The context, the owners of its HIP resources and the entry points'
@@ -478,6 +479,41 @@ int launch_decompress_region(myyuv_hip_ctx* c, const FrameGeom& G, const FrameGe
               c->qtd.as<const QTables>(), static_cast<uint8_t*>(d_out), err);
   return e ? MYYUV_E_HIP : 0;
 }
+
+// Scaled decode (denom 2, 4 or 8): payload f at d_in + f * cap -> the scaled
+// frame f at d_out + f * G.fbytes / denom^2.  The scan as launch_decompress
+// runs it, then k_decode_scaled<8 / denom> on k_decode_idct's grid, whatever
+// MYYUV_DECODER says (there is no split form).  Workspace: reserve_scaled.
+int reserve_scaled(myyuv_hip_ctx* c, const FrameGeom& G) {
+  const uint32_t nwaves = ceil_div(G.cum[3] * G.nframes, kWave);
+  if (c->coef.grow((size_t)nwaves * kCoefQuadsPerWave * 16)) return MYYUV_E_HIP;  // (decode_general's blocks)
+  return reserve_scan(c, G);
+}
+
+int launch_decompress_scaled(myyuv_hip_ctx* c, const FrameGeom& G, uint32_t denom, const void* d_in,
+                             const uint32_t* d_size, uint32_t cap, void* d_out, hipStream_t s) {
+  const uint32_t nf = G.nframes;
+  const uint32_t ntiles = ceil_div(G.cum[3], kScanTile);
+  unsigned long long* err = c->err.as<unsigned long long>();
+  StreamDesc* desc = c->desc.as<StreamDesc>();
+  const uint8_t* in = static_cast<const uint8_t*>(d_in);
+  int e = 0;
+  ScanSrc SS;
+  for (int i = 0; i < 4; i++) SS.cum[i] = G.cum[i];
+  for (int p = 0; p < 3; p++) SS.pos[p] = 0;
+  e |= launch(c, MYYUV_K_SCAN, k_scan_chain, dim3(ntiles, nf), dim3(256), s, in, cap, SS, d_size, cap, G, desc,
+              c->loff.as<uint32_t>(), c->tiles.as<uint32_t>(), ntiles, c->status.as<unsigned long long>(),
+              next_epoch(c), err);
+  const uint32_t t0 = ceil_div(G.cum[1] - G.cum[0], kWave), t1 = ceil_div(G.cum[2] - G.cum[1], kWave),
+                 t2 = ceil_div(G.cum[3] - G.cum[2], kWave);
+  auto* k = denom == 2 ? k_decode_scaled<4> : (denom == 4 ? k_decode_scaled<2> : k_decode_scaled<1>);
+  e |= launch(c, MYYUV_K_SCALED, k, dim3(t0 + t1 + t2, nf), dim3(kWave), s, in, d_size, cap,
+              (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, t0, t1,
+              c->qtd.as<const QTables>(), c->coef.as<uint4>(), static_cast<uint8_t*>(d_out), err);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+bool denom_ok(uint32_t denom) { return denom == 2 || denom == 4 || denom == 8; }
 
 // Host <-> device copies of the host-buffer entry points: direct async copies
 // from / into the caller's pageable buffers.  On this stack they run at the
@@ -1031,6 +1067,111 @@ int myyuv_gpu_dct_decompress_region_to_bmp(myyuv_hip_handle c, const uint8_t* pa
   if (c->bmp.grow(out_bytes)) return MYYUV_E_HIP;
   if ((e = region_to_frame(c, payload, size, G, R, S, q, s)) ||
       (e = launch_to_bmp(c, c->frame.p, rw, rh, 1, orient, bit_count, chroma, c->bmp.p, s)))
+    return e;
+  if ((e = read_err(c, s, bad_block))) {
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  if (d2h(bmp_data, c->bmp.p, out_bytes, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+// ---- scaled decode (defined in myyuv_hip.h) ---------------------------------
+namespace {
+
+// The host-buffer scaled calls' device part: the stream goes up, the scaled
+// frame (G.fbytes / denom^2 bytes) is left in the context's `frame` buffer.
+int scaled_to_frame(myyuv_hip_ctx* c, const uint8_t* payload, uint32_t size, const FrameGeom& G, uint32_t denom,
+                    const uint8_t q[3], hipStream_t s) {
+  int e;
+  const uint32_t cap = (size + 3) & ~3u;
+  if ((e = reserve_scaled(c, G)) || (e = set_qtables(c, q, s))) return e;
+  if (c->frame.grow(G.fbytes / (denom * denom)) || c->payload.grow(cap)) return MYYUV_E_HIP;
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (hipMemsetAsync(static_cast<uint8_t*>(c->payload.p) + (cap - 4), 0, 4, s) != hipSuccess ||
+      h2d(c->payload.p, payload, size, s) ||
+      hipMemcpyAsync(c->psize.p, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  return launch_decompress_scaled(c, G, denom, c->payload.p, c->psize.as<const uint32_t>(), cap, c->frame.p, s);
+}
+
+}  // namespace
+
+int myyuv_gpu_dct_decompress_scaled(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w,
+                                    uint32_t h, const uint8_t q[3], uint32_t denom, uint8_t* iyuv,
+                                    int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payload || !iyuv || !q) return MYYUV_E_ARG;
+  int e = check_q(q);
+  if (e) return e;
+  FrameGeom G;
+  if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G))) return e;
+  if (!denom_ok(denom)) return MYYUV_E_ARG;
+  Entry en(c);
+  hipStream_t s = en.s;
+  if ((e = scaled_to_frame(c, payload, size, G, denom, q, s))) return e;
+  if ((e = read_err(c, s, bad_block))) {
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  if (d2h(iyuv, c->frame.p, G.fbytes / (denom * denom), s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+int myyuv_gpu_dct_decompress_scaled_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_sizes,
+                                           uint32_t cap, uint32_t nframes, uint32_t w, uint32_t h,
+                                           const uint8_t q[3], uint32_t denom, void* d_iyuv, void* stream) {
+  if (!c || !d_payload || !d_sizes || !d_iyuv || !q) return MYYUV_E_ARG;
+  // (d_iyuv: the kernel's 2- and 4-byte row stores)
+  if (((uintptr_t)d_payload & 3) || ((uintptr_t)d_iyuv & 3) || (nframes > 1 && (cap & 3))) return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = check_q(q);
+  if (e || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes))) return e;
+  if (!denom_ok(denom)) return MYYUV_E_ARG;
+  Entry en(c, stream);
+  // (as several launches past the kernels' 32-bit block numbers or the grid's 65,535 frames)
+  const uint32_t per = std::min(launch_frames(G, c->launch_blocks), 65535u);
+  FrameGeom GL = G;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve_scaled(c, GL)) || (e = set_qtables(c, q, en.s)))
+    return e;
+  const size_t sbytes = G.fbytes / (denom * denom);
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GL.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
+    const uint8_t* pay = static_cast<const uint8_t*>(d_payload) + (size_t)f0 * cap;
+    uint8_t* fr = static_cast<uint8_t*>(d_iyuv) + (size_t)f0 * sbytes;
+    if ((e = launch_decompress_scaled(c, GL, denom, pay, d_sizes + f0, cap, fr, en.s))) return e;
+  }
+  return 0;
+}
+
+int myyuv_gpu_dct_decompress_scaled_to_bmp(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, int32_t width,
+                                           int32_t height, const uint8_t q[3], uint32_t denom, uint16_t bit_count,
+                                           uint32_t chroma, uint8_t* bmp_data, int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payload || !bmp_data || !q || !chroma_ok(chroma)) return MYYUV_E_ARG;
+  int e = check_q(q);
+  if (e) return e;
+  FrameGeom G;
+  const uint32_t w = width < 0 ? 0u - (uint32_t)width : (uint32_t)width;
+  const uint32_t h = height < 0 ? 0u - (uint32_t)height : (uint32_t)height;
+  if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G))) return e;
+  if (!denom_ok(denom)) return MYYUV_E_ARG;
+  // K8's checks on the scaled frame's signed header fields (exact: |width|
+  // and |height| are multiples of 16)
+  uint32_t sw = 0, sh = 0, orient = 0;
+  if ((e = bmp_check(width / (int32_t)denom, height / (int32_t)denom, bit_count, &sw, &sh, &orient))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const size_t out_bytes = (size_t)sw * sh * (bit_count / 8);
+  if (c->bmp.grow(out_bytes)) return MYYUV_E_HIP;
+  if ((e = scaled_to_frame(c, payload, size, G, denom, q, s)) ||
+      (e = launch_to_bmp(c, c->frame.p, sw, sh, 1, orient, bit_count, chroma, c->bmp.p, s)))
     return e;
   if ((e = read_err(c, s, bad_block))) {
     (void)reset_err(c, s);

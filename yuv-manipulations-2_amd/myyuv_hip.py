@@ -22,10 +22,10 @@ CHROMA_NEAREST, CHROMA_LINEAR = 0, 1  # MYYUV_CHROMA_*
 
 KERNELS = ["fdct_quant", "huff_encode", "scan_tiles", "stream_out", "encode_tile", "huff_decode",
            "dequant_idct", "huff_encode_wide", "huff_encode_r16", "huff_encode_wave", "bmp_to_iyuv",
-           "fdct_fix", "iyuv_to_bmp", "decode_region"]
+           "fdct_fix", "iyuv_to_bmp", "decode_region", "decode_scaled"]
 # ids: MYYUV_K_* of include/myyuv_hip.h, in KERNELS order (tests/test_cabi.py checks both)
 (K_FDCT, K_HUFF_ENC, K_SCAN, K_COMPACT, K_ENCODE_TILE, K_HUFF_DEC, K_IDCT, K_HUFF_WIDE,
- K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP, K_REGION) = range(len(KERNELS))
+ K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP, K_REGION, K_SCALED) = range(len(KERNELS))
 
 # the exported symbols include/myyuv_hip.h declares (checked by the CPU tests)
 EXPORTS = [
@@ -40,6 +40,8 @@ EXPORTS = [
     "myyuv_gpu_dct_decompress_to_bmp", "myyuv_gpu_dct_decompress_to_bmp_frames",
     "myyuv_gpu_dct_decompress_region", "myyuv_gpu_dct_decompress_region_device",
     "myyuv_gpu_dct_decompress_region_to_bmp",
+    "myyuv_gpu_dct_decompress_scaled", "myyuv_gpu_dct_decompress_scaled_device",
+    "myyuv_gpu_dct_decompress_scaled_to_bmp",
 ]
 
 _lib = None
@@ -128,6 +130,9 @@ def load():
                                                          vp, vp]
     L.myyuv_gpu_dct_decompress_region_to_bmp.argtypes = [vp, u8p, u32, i32, i32, u8p, u32, u32, u32, u32, u16, u32,
                                                          u8p, i64p]
+    L.myyuv_gpu_dct_decompress_scaled.argtypes = [vp, u8p, u32, u32, u32, u8p, u32, u8p, i64p]
+    L.myyuv_gpu_dct_decompress_scaled_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, u32, vp, vp]
+    L.myyuv_gpu_dct_decompress_scaled_to_bmp.argtypes = [vp, u8p, u32, i32, i32, u8p, u32, u16, u32, u8p, i64p]
     L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -455,6 +460,55 @@ class Codec:
         rc = load().myyuv_gpu_dct_decompress_region_to_bmp(self._h, _u8(src), src.size, int(width), int(height),
                                                            _u8(_q(q)), rx, ry, rw, rh, int(bit_count), int(chroma),
                                                            _u8(out), ctypes.byref(bad))
+        if rc:
+            raise CodecError(rc, bad.value)
+        return out[:n].tobytes()
+
+    # -- scaled decode: denom = 2, 4 or 8, a (w/denom) x (h/denom) frame from the
+    # low-frequency corner of every block (defined in include/myyuv_hip.h) --
+    def decompress_scaled(self, payload, w, h, q, denom):
+        """DCTYUV payload -> the (w/denom) x (h/denom) IYUV frame, as bytes."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        d = int(denom)
+        n = int(w) * int(h) * 3 // 2 // (d * d) if d in (2, 4, 8) else 0
+        out = np.empty(max(1, n), np.uint8)
+        self.decompress_scaled_into(src, w, h, q, d, out)
+        return out[:n].tobytes()
+
+    def decompress_scaled_into(self, payload, w, h, q, denom, out):
+        """decompress_scaled from / into the caller's C-contiguous uint8 arrays
+        (`out` at least w*h*3/2/denom^2 bytes; untouched when the call fails)."""
+        src = _u8_array(payload, "payload")
+        dst = _u8_array(out, "out", writable=True)
+        d = int(denom)
+        if d in (2, 4, 8) and dst.nbytes < int(w) * int(h) * 3 // 2 // (d * d):
+            raise ValueError("output smaller than w*h*3/2/denom^2")
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_decompress_scaled(self._h, _u8(src), src.nbytes, w, h, _u8(_q(q)), d, _u8(dst),
+                                                    ctypes.byref(bad))
+        if rc:
+            raise CodecError(rc, bad.value)
+
+    def decompress_scaled_device(self, d_payload, d_sizes, cap, nframes, w, h, q, denom, d_iyuv, stream=None):
+        """Device-resident batch: stream f at d_payload + f*cap -> scaled frame
+        f at d_iyuv + f*(w*h*3/2/denom^2); asynchronous, errors through
+        sync_status."""
+        rc = load().myyuv_gpu_dct_decompress_scaled_device(self._h, d_payload, d_sizes, cap, nframes, w, h,
+                                                           _u8(_q(q)), int(denom), d_iyuv, stream)
+        if rc:
+            raise CodecError(rc)
+
+    def decompress_scaled_to_bmp(self, payload, width, height, q, denom, bit_count=32, chroma=CHROMA_LINEAR):
+        """decompress_scaled, then iyuv_to_bmp of the scaled frame on the
+        device (width / height signed: the orientation of the BMP written)."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        d = int(denom)
+        n = (abs(int(width)) // d) * (abs(int(height)) // d) * (int(bit_count) // 8) if d in (2, 4, 8) else 0
+        out = np.empty(max(1, n), np.uint8)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_decompress_scaled_to_bmp(self._h, _u8(src), src.size, int(width), int(height),
+                                                           _u8(_q(q)), d, int(bit_count), int(chroma), _u8(out),
+                                                           ctypes.byref(bad))
         if rc:
             raise CodecError(rc, bad.value)
         return out[:n].tobytes()
