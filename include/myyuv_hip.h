@@ -86,7 +86,34 @@ int myyuv_gpu_dct_compress(myyuv_hip_handle h, const uint8_t* iyuv, uint32_t wid
  * (myyuv_yuv.cpp:148-158).  Writes W*H*3/2 bytes to `iyuv`.  On a decode error
  * returns its code; *bad_block (optional) receives the global block index
  * (plane-major, row-major blocks) of the first failing block, -1 for header
- * errors. */
+ * errors.
+ *
+ * Order of checks (every decompress call; the CPU restatement
+ * oracle/myyuv_oracle.c follows it, the reference is undefined past its own
+ * load checks):
+ *   1. the handle and pointers (MYYUV_E_ARG), then the quality;
+ *   2. the whole stream header, before any chunk is looked at: size <= 12 and
+ *      12 + ps0 + ps1 + ps2 > size (6), then plane by plane ps <= 8 (7),
+ *      chunk-size count 0 (8), content_size 0 (9), 8 + count + content_size >
+ *      ps (7), all in 64-bit arithmetic; then the % 8 dimension checks (3, 4);
+ *      then, plane by plane, a chunk-size count below the plane's block count
+ *      (8).  *bad_block = -1 for all of these;
+ *   3. plane by plane: the plane-content check (the chunk sizes of the
+ *      plane's blocks sum to more than content_size:
+ *      MYYUV_E_PLANE_CONTENT), which fails the plane as a whole, before any
+ *      of its chunks; then the plane's chunks in block order (10, 11, 12).
+ *      The lowest failing block is reported, whichever kernel lane found it.
+ * *bad_block for MYYUV_E_PLANE_CONTENT from step 3 is the first block of the
+ * failing plane (the count of blocks in the planes before it), and -1 when
+ * that is block 0 of the call's first frame: the device's error key 0 means
+ * "no block".  A chunk error in an earlier plane comes first; a chunk error in
+ * the same plane, at whatever block, does not.
+ *
+ * Table limits (step 3's chunk checks, MYYUV_E_BAD_CHUNK): a chunk's Huffman
+ * table may hold at most 64 entries per code length, in any number of
+ * groups; the total over all lengths is limited only by table_bytes (the
+ * reference's Huffman::fromDump has no limit; a message has at most 64
+ * symbols, so more than 64 entries of one length cannot all be used). */
 int myyuv_gpu_dct_decompress(myyuv_hip_handle h, const uint8_t* payload, uint32_t size,
                              uint32_t width, uint32_t height, const uint8_t quality[3],
                              uint8_t* iyuv, int64_t* bad_block);
@@ -98,7 +125,11 @@ int myyuv_gpu_dct_decompress(myyuv_hip_handle h, const uint8_t* payload, uint32_
  *   compress:   d_iyuv (W*H*3/2 B) -> d_payload (cap B), *d_payload_size (u32, device)
  *   decompress: d_payload + *d_payload_size (device u32) -> d_iyuv
  * Errors found on the device are collected in the context and returned by
- * myyuv_hip_sync_status. */
+ * myyuv_hip_sync_status.  The decompress calls (these, the batch, region and
+ * scaled ones) read a stream inside min(size word, cap) only: a size word
+ * above cap decodes as the stream cut at cap, and bytes past the size word
+ * never matter.  Every stream check of myyuv_gpu_dct_decompress's step 2
+ * runs on the device here, in the same order. */
 int myyuv_hip_reserve(myyuv_hip_handle h, uint32_t width, uint32_t height);
 int myyuv_gpu_dct_compress_device(myyuv_hip_handle h, const void* d_iyuv, uint32_t width,
                                   uint32_t height, const uint8_t quality[3], void* d_payload,

@@ -645,11 +645,22 @@ int oracle_compress(const uint8_t* iyuv, uint32_t w, uint32_t h, const uint8_t q
 }
 
 /* DCTYUV::load + DCTYUVPlane::load size checks (DCT.cpp:39-62, :130-159),
- * then per plane the dims check and the block loop.  Stricter than the
+ * the dimension checks, then per plane the block loop.  Stricter than the
  * reference where it is undefined: a zero plane size, fewer chunk sizes than
- * blocks, or chunk sizes summing past content_size are errors here. */
-int oracle_decompress(const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
-                      const uint8_t q[3], uint8_t* iyuv) {
+ * blocks, or chunk sizes summing past content_size are errors here.
+ *
+ * The order of checks is the one include/myyuv_hip.h writes down for
+ * myyuv_gpu_dct_decompress: quality; the whole stream header (every plane's,
+ * "fewer chunk sizes than blocks" included) before any chunk is looked at;
+ * then plane by plane the content check (the plane's chunk sizes against its
+ * content_size: the plane fails as a whole, before any of its chunks) and its
+ * chunks in block order.  *bad_block (optional): -1 for the header errors,
+ * the plane's first block for ORACLE_E_PLANE_CONTENT (-1 when that is block
+ * 0: the C ABI's error key 0 means "no block"), else the lowest failing
+ * block's plane-major, row-major index. */
+int oracle_decompress_ex(const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                         const uint8_t q[3], uint8_t* iyuv, int64_t* bad_block) {
+    if (bad_block) *bad_block = -1;
     for (int p = 0; p < 3; p++)
         if (q[p] < 1 || q[p] > 100) return ORACLE_E_QUALITY;
     if (size <= 12) return ORACLE_E_DCTYUV_SIZE;
@@ -670,14 +681,19 @@ int oracle_decompress(const uint8_t* payload, uint32_t size, uint32_t w, uint32_
         if (hc[p] == 0) return ORACLE_E_PLANE_CONTENT;
         if (8 + (uint64_t)hn[p] + hc[p] > ps[p]) return ORACLE_E_PLANE_SIZE;
     }
+    int e = check_dims(w, h);
+    if (e) return e;
+    for (int p = 0; p < 3; p++) {
+        uint32_t pw, ph;
+        plane_dims(w, h, p, &pw, &ph);
+        if (hn[p] < (pw / 8) * (ph / 8)) return ORACLE_E_PLANE_NBLK;
+    }
     int err = 0;
+    int64_t cum = 0; /* blocks of the planes before p */
     for (int p = 0; p < 3 && !err; p++) {
         uint32_t pw, ph;
         plane_dims(w, h, p, &pw, &ph);
-        if (pw % 8 != 0) return ORACLE_E_WIDTH;
-        if (ph % 8 != 0) return ORACLE_E_HEIGHT;
         uint32_t bw = pw / 8, bh = ph / 8, nblk = bw * bh;
-        if (hn[p] < nblk) return ORACLE_E_PLANE_NBLK;
         const uint8_t* sizes = payload + poff[p] + 8;
         const uint8_t* content = sizes + hn[p];
         uint32_t* pos = (uint32_t*)malloc((size_t)nblk * 4);
@@ -688,6 +704,7 @@ int oracle_decompress(const uint8_t* payload, uint32_t size, uint32_t w, uint32_
         }
         if (acc > hc[p]) {
             free(pos);
+            if (bad_block) *bad_block = cum == 0 ? -1 : cum;
             return ORACLE_E_PLANE_CONTENT;
         }
         float Q[64];
@@ -700,12 +717,12 @@ int oracle_decompress(const uint8_t* payload, uint32_t size, uint32_t w, uint32_
             uint32_t by = (uint32_t)k / bw, bx = (uint32_t)k % bw;
             int16_t c[64];
             uint8_t px[64];
-            int e = oracle_huff_decode_block(content + pos[k], sizes[k], c);
-            if (e) {
+            int be = oracle_huff_decode_block(content + pos[k], sizes[k], c);
+            if (be) {
 #pragma omp critical
                 if (k < bad_blk) {
                     bad_blk = k;
-                    bad_err = e;
+                    bad_err = be;
                 }
             }
             oracle_idct_block(c, Q, px);
@@ -713,8 +730,15 @@ int oracle_decompress(const uint8_t* payload, uint32_t size, uint32_t w, uint32_
         }
         free(pos);
         err = bad_err;
+        if (err && bad_block) *bad_block = cum + bad_blk;
+        cum += nblk;
     }
     return err;
+}
+
+int oracle_decompress(const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                      const uint8_t q[3], uint8_t* iyuv) {
+    return oracle_decompress_ex(payload, size, w, h, q, iyuv, NULL);
 }
 
 int oracle_num_threads(void) {

@@ -42,6 +42,12 @@ int oracle_compress(const uint8_t* iyuv, uint32_t w, uint32_t h, const uint8_t q
                     uint8_t* payload, uint32_t cap, uint32_t* out_size);
 int oracle_decompress(const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
                       const uint8_t q[3], uint8_t* iyuv);
+/* oracle_decompress, with *bad_block (optional) as include/myyuv_hip.h defines
+ * it for myyuv_gpu_dct_decompress: -1 for header errors, the plane's first
+ * block (-1 when that is block 0) for ORACLE_E_PLANE_CONTENT, else the lowest
+ * failing block's plane-major, row-major index. */
+int oracle_decompress_ex(const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                         const uint8_t q[3], uint8_t* iyuv, int64_t* bad_block);
 int oracle_bmp_to_iyuv(const uint8_t* bmp_data, int32_t width, int32_t height, uint32_t bit_count,
                        uint8_t* iyuv);
 int oracle_num_threads(void);

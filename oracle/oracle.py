@@ -65,6 +65,23 @@ def decompress(payload, w, h, q):
     return out.tobytes()
 
 
+def decompress_ex(payload, w, h, q):
+    """(code, bad_block, frame): `decompress` without the exception, with the
+    failing block as include/myyuv_hip.h defines *bad_block for
+    myyuv_gpu_dct_decompress (-1: none / a header error).  frame is None when
+    code != 0."""
+    src = np.frombuffer(bytes(payload), np.uint8)
+    qa = np.array(q, np.uint8)
+    out = np.zeros(w * h * 3 // 2, np.uint8)
+    bad = ctypes.c_int64(-1)
+    L = lib()
+    L.oracle_decompress_ex.argtypes = [ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8),
+                                       ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64)]
+    rc = L.oracle_decompress_ex(_p(src), len(src), w, h, _p(qa), _p(out), ctypes.byref(bad))
+    return rc, bad.value, (None if rc else out.tobytes())
+
+
 def qtable(q, chroma):
     out = np.empty(64, np.float32)
     lib().oracle_qtable(int(q), int(chroma), _p(out, ctypes.c_float))

@@ -250,17 +250,13 @@ def test_decode_errors_match_oracle(codec, oracle, golden, gold):
     g = golden(gold)
     w, h, q = g.width, g.height, tuple(g.params)
     for name, pay, kind in malformed.cases(g.data):
-        try:
-            oracle.decompress(pay, w, h, q)
-            exp = 0
-        except RuntimeError as e:
-            exp = e.args[0]
+        exp, exp_bad, _ = oracle.decompress_ex(pay, w, h, q)
         try:
             codec.decompress(pay, w, h, q)
-            got = 0
+            got, got_bad = 0, -1
         except myyuv_hip.CodecError as e:
-            got = e.code
-        assert got == exp, (name, got, exp)
+            got, got_bad = e.code, e.bad_block
+        assert (got, got_bad) == (exp, exp_bad), (name, got, got_bad, exp, exp_bad)
         assert exp != 0, name
 
 

@@ -26,4 +26,16 @@ for r in rows:
     if re.search(sys.argv[1], n):
         print("%-28s vgpr %4s spill %3s scratch %4s lds %6s sgpr %s" % (n, r["vgpr_count"], r["vgpr_spill_count"], r["private_segment_fixed_size"], r["group_segment_fixed_size"], r["sgpr_count"]))
 ' "$filt"
+# code size: the kernels' function symbols of the code object
+$L/llvm-readelf --symbols --wide $d/k.co | python3 -c '
+import sys, re
+seen = set()  # (.dynsym and .symtab list each kernel)
+for l in sys.stdin:
+    f = l.split()
+    if len(f) == 8 and f[3] == "FUNC" and f[7].startswith("_ZN9myyuv_gpu") and f[7] not in seen:
+        seen.add(f[7])
+        n = re.sub(r"^_ZN9myyuv_gpu\d+", "", f[7])[:28]
+        if re.search(sys.argv[1], n):
+            print("%-28s code %6d B" % (n, int(f[2])))
+' "$filt"
 rm -rf $d

@@ -159,13 +159,12 @@ __device__ __forceinline__ int parse_table(const Chunk& c, uint32_t s, Table& T,
     return (w >> (8u * (i & 3u))) & 0xFFu;
   };
   uint64_t cnt = 0, glo = 0, ghi = 0;
-  uint32_t seen = 0, total = 0, i = 3;
+  uint32_t seen = 0, i = 3;
   bool regular = true, bad = bad_hdr;
   auto group = [&](uint32_t info) {  // the group whose info byte is at i
     const uint32_t L = (info >> 5) + 1, n = (info & 31) + 1;
     const uint32_t nbytes = (n * 11 + 7) / 8;
-    total += n;
-    bad = bad || i + 1 + nbytes > 3 + tb || total > 64;
+    bad = bad || i + 1 + nbytes > 3 + tb;
     cnt += (uint64_t)n << (8 * (L - 1));
     regular = regular && !(seen & (1u << L));
     seen |= 1u << L;
@@ -179,6 +178,11 @@ __device__ __forceinline__ int parse_table(const Chunk& c, uint32_t s, Table& T,
   } else {
     while (i - 3 < tb && !bad) group(c.byte(i));
   }
+  // at most 64 entries per code length (include/myyuv_hip.h, "Table limits";
+  // the total is limited by tb alone: 255 table bytes hold fewer than 186
+  // entries, so no byte of cnt carries into the next).  One test of the eight
+  // counts after the walk: a byte above 64 has bit 7 set once 63 is added.
+  bad = bad || ((cnt + 0x3F3F3F3F3F3F3F3Full) & 0x8080808080808080ull) != 0;
   uint32_t F = 0;
 #pragma unroll
   for (int L = 0; L < 8; L++) {  // length L + 1

@@ -168,11 +168,13 @@ int check_q(const uint8_t q[3]) {
 
 // The kernels' error word (record_error, k_stream.hip) -> code, with the
 // failing block counted from the call's first frame: the launch began at
-// frame f0, nblk blocks per frame.  ~0: no error; a key of 0: no block.
+// frame f0, nblk blocks per frame.  ~0: no error; a key of 0 in a launch
+// that began at the call's first frame: no block (a later launch's key 0 is
+// its first frame's block 0, as in a launch that holds the whole batch).
 int chunk_err(unsigned long long v, uint32_t f0, uint32_t nblk, int64_t* bad_block) {
   if (v == ~0ull) return 0;
   const uint64_t key = v >> 8;
-  if (bad_block) *bad_block = key == 0 ? -1 : (int64_t)(key >> 1) + (int64_t)f0 * nblk;
+  if (bad_block) *bad_block = key == 0 && f0 == 0 ? -1 : (int64_t)(key >> 1) + (int64_t)f0 * nblk;
   return (int)(v & 0xFF);
 }
 
