@@ -174,6 +174,14 @@ struct QTables {
   float kb[3][8];     // K1's fast-path bound per row (fdct_bfly.h bfly_row_bounds)
 };
 
+// The requantiser's tables (a device buffer of their own; k_requant stages the
+// workgroup's plane of both into LDS): the source and the destination quality's
+// Q tables, natural order, as QTables::q.
+struct RequantTables {
+  float qs[3][64];
+  float qd[3][64];
+};
+
 // K1's near-tie window per unit of |t| (k_transform.hip): t = y * fl(1/Q)
 // may differ from fl(y / Q) by |t| * 1.5 * 2^-23; 2^-21 covers it with margin
 // (tools/check_numerics.c checks every Q at every tie; 2^-24 already fails).

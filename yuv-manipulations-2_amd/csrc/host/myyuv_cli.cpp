@@ -22,6 +22,10 @@
 // corner, on the GPU; not combined with -crop):
 //   myyuv_cli in.myyuv -decompress -scale 1/2|1/4|1/8 -o out.myyuv
 //   myyuv_cli in.myyuv -to_bmp [24|32] [-chroma nearest|linear] -scale 1/2|1/4|1/8 -o out.bmp
+// a compressed input re-encoded at another quality on its coefficients
+// (requantise, include/myyuv_hip.h: no pixels in between; the qualities parse
+// and fill as -compress DCT's):
+//   myyuv_cli in.myyuv -requantize q [q [q]] -o out.myyuv
 // and, beyond the reference CLI, many frames per invocation (SURVEY.md §8f
 // row 2; frames of one geometry share batched kernel launches):
 //   myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IN.myyuv...
@@ -60,6 +64,8 @@ void usage() {
             << "  myyuv_cli IMAGE.myyuv -decompress -scale 1/2|1/4|1/8 -o OUT.myyuv\n"
             << "  myyuv_cli IMAGE.myyuv -to_bmp [24|32] [-chroma nearest|linear] -scale 1/2|1/4|1/8 -o OUT.bmp\n"
             << "      (-scale: a compressed image at that size, straight from its DCT coefficients)\n"
+            << "  myyuv_cli IMAGE.myyuv -requantize Q [Q [Q]] -o OUT.myyuv\n"
+            << "      (a compressed image at another quality, straight from its DCT coefficients)\n"
             << "  myyuv_cli IMAGE.bmp -info\n"
             << "  myyuv_cli IMAGE.bmp -to_yuv IYUV -o OUT.myyuv\n"
             << "  myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IMAGE.myyuv...\n"
@@ -114,17 +120,22 @@ const char* take_scale(std::vector<std::string>& args, size_t a, uint32_t& denom
   return nullptr;
 }
 
-myyuv::YUV compress_dct(const myyuv::YUV& yuv, const std::vector<std::string>& params) {
+// One to three DCT qualities, the last one repeated (main.cpp:64-75).
+void dct_qualities(const std::vector<std::string>& params, uint8_t q[3]) {
   if (params.size() > 3)
     throw std::runtime_error("Error. Too many compression parameters. Can't be more than 3 parameters.");
   if (params.empty()) throw std::runtime_error("Error. Too few compression parameters. Must be at least one.");
-  uint8_t q[3];
   for (size_t i = 0; i < 3; i++) {
     const int v = std::stoi(params[i < params.size() ? i : params.size() - 1]);
     if (v < 1 || v > 100)
       throw std::runtime_error("Error. Compression parameters for DCT must range between [1..100].");
     q[i] = (uint8_t)v;
   }
+}
+
+myyuv::YUV compress_dct(const myyuv::YUV& yuv, const std::vector<std::string>& params) {
+  uint8_t q[3];
+  dct_qualities(params, q);
   return yuv.compress(myyuv::YUV::Compressions::DCT, q, 3);
 }
 
@@ -178,6 +189,32 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     myyuv::YUV out;
     const float ms = elapsed_ms([&] { out = compress_dct(yuv, params); });
     std::cout << "YUV DCT compression (" << label << ") : " << ms << " ms\n";
+    out.dump(args[a]);
+    return 0;
+  }
+  if (cmd == "-requantize") {  // Q [Q [Q]] -o OUT.myyuv: the qualities as -compress DCT's
+    if (!yuv.isCompressed()) {
+      std::cout << "Nothing to requantize, image is not compressed (-requantize needs DCT coefficients)\n";
+      return 1;
+    }
+    a++;
+    std::vector<std::string> params;
+    while (a < args.size() && args[a] != "-o") params.push_back(args[a++]);
+    a++;
+    if (a >= args.size() || args.size() != a + 1) {
+      std::cout << "Invalid argument, last arguments must be `-o /path/to/new_image.myyuv`\n";
+      usage();
+      return 1;
+    }
+    std::string label = " ";
+    for (const auto& p : params) label += p + " ";
+    myyuv::YUV out;
+    const float ms = elapsed_ms([&] {
+      uint8_t q[3];
+      dct_qualities(params, q);
+      out = myyuvDCT::requantize_DCT_planar(yuv, {q[0], q[1], q[2]});
+    });
+    std::cout << "YUV DCT requantization (" << label << ") : " << ms << " ms\n";
     out.dump(args[a]);
     return 0;
   }

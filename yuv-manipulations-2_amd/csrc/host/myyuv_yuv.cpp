@@ -639,6 +639,42 @@ myyuv::YUV decompress_DCT_planar_scaled(const myyuv::YUV& yuv, uint32_t denom) {
   return res;
 }
 
+// Requantise (include/myyuv_hip.h): the checks of decompress_DCT_planar_region
+// on the input, the new qualities' range as compress_DCT_planar checks it, and
+// compress_DCT_planar's header rewrite with the new quality bytes.
+myyuv::YUV requantize_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 3>& params) {
+  using myyuv::YUV;
+  if (yuv.getFormatGroup() != YUV::FormatGroup::PLANAR)
+    throw std::runtime_error("Error decompressing: YUV must be planar");
+  if (yuv.getCompression() != YUV::Compressions::DCT)
+    throw std::runtime_error("Error this decompression is unimplemented");
+  if (yuv.header.compression_params_size != 3 || !yuv.compression_params)
+    throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
+  for (int p = 0; p < 3; p++)
+    if (yuv.compression_params[p] < 1 || yuv.compression_params[p] > 100)
+      throw std::runtime_error("Level of quality must be between 1 and 100");
+  for (uint8_t q : params)
+    if (q < 1 || q > 100) throw std::runtime_error("Level of quality must be between 1 and 100");
+  const uint32_t w = yuv.header.width, h = yuv.header.height;
+  std::vector<uint8_t> payload(myyuv_dct_payload_bound(w, h));
+  uint32_t size = 0;
+  int64_t bad = -1;
+  const int rc = myyuv_gpu_dct_requantize(t_codec.get(), yuv.data, yuv.header.data_size, w, h, yuv.compression_params,
+                                          params.data(), payload.data(), (uint32_t)payload.size(), &size, &bad);
+  if (rc) fail(rc);
+  YUV res;
+  res.header = yuv.header;
+  res.header.compression = YUV::Compressions::DCT;
+  res.header.compression_params_size = 3;
+  res.header.compression_params_pos = sizeof(myyuv::YUVHeader);
+  res.header.data_pos = sizeof(myyuv::YUVHeader) + 3;
+  res.header.data_size = size;
+  res.compression_params = new uint8_t[3]{params[0], params[1], params[2]};
+  res.data = new uint8_t[size ? size : 1];
+  std::memcpy(res.data, payload.data(), size);
+  return res;
+}
+
 // Many compressed frames per call. Each frame is checked as YUV::decompress
 // -> decompress_map[DCT][IYUV] -> decompress_DCT_planar would, in input order
 // (frames that are not DCT / IYUV, or fail a check, take that single-frame

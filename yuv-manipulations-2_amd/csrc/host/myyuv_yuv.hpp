@@ -140,6 +140,12 @@ myyuv::YUV decompress_DCT_planar_region(const myyuv::YUV& yuv, uint32_t rx, uint
 // frame, denom 2, 4 or 8, from the low-frequency corner of every block.
 // decompress_DCT_planar's checks; its header with the scaled size.
 myyuv::YUV decompress_DCT_planar_scaled(const myyuv::YUV& yuv, uint32_t denom);
+// Requantise (include/myyuv_hip.h): the DCT-compressed frame re-encoded at the
+// qualities `params` on its coefficients, no pixels in between.  The source
+// qualities are the frame's compression parameters.  decompress_DCT_planar's
+// checks and messages for the input (an input that is not DCT-compressed is
+// refused); compress_DCT_planar's header with the three new quality bytes.
+myyuv::YUV requantize_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 3>& params);
 // Many frames per call: frames of one geometry share
 // one batched launch of every kernel; result i is compress_DCT_planar(*frames[i]).
 std::vector<myyuv::YUV> compress_DCT_planar_batch(const std::vector<const myyuv::YUV*>& frames,

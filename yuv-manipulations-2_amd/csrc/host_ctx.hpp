@@ -36,6 +36,9 @@ template <int N>
 __global__ void k_decode_scaled(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
                                 const uint32_t*, FrameGeom, uint32_t, uint32_t, const QTables*, uint4*, uint8_t*,
                                 unsigned long long*);
+__global__ void k_requant(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
+                          const uint32_t*, FrameGeom, uint32_t, uint32_t, const RequantTables*, uint4*, uint8_t*,
+                          uint32_t*, unsigned long long*);
 template <uint32_t W>
 __global__ void k_huff_encode(const uint4*, const uint32_t*, const uint4*, FrameGeom, uint32_t*, uint32_t*,
                               uint8_t*, uint32_t*, uint32_t*, uint32_t*);
@@ -176,6 +179,15 @@ struct myyuv_hip_ctx {
   hipStream_t qt_stream = nullptr;
   uint8_t q_cached[3] = {0, 0, 0};
   bool q_valid = false;
+  // the requantiser's two tables (RequantTables), cached the same way by the
+  // (source, destination) quality triples; its own buffer, so qt / qtd and
+  // their cache are untouched by a requantise call.  rqsrc: the host-buffer
+  // call's staged source stream (`payload` takes its result)
+  DevBuf rqt, rqsrc;
+  RequantTables rq;
+  hipStream_t rq_stream = nullptr;
+  uint8_t rq_cached[6] = {0, 0, 0, 0, 0, 0};
+  bool rq_valid = false;
   // profiling: the kernels' start/stop events until drain_profile reads
   // them; they are used again from launch to launch
   struct Stamp {

@@ -34,8 +34,10 @@
 //   words (the de-zig-zag of Huffman.cpp:148-153 is free) and the block is
 //   written as 8 quads of the codec_common.hpp layout that K6 reads.
 #include "codec_common.hpp"
+#include "huff_common.hpp"
 #include "idct_scaled.h"
 #include "k_stream.hpp"
+#include "requant.h"
 #include "xform_common.hpp"
 
 namespace myyuv_gpu {
@@ -76,15 +78,7 @@ constexpr uint32_t kGposQuads = 8 * 64 * 4 / 16;
 
 
 
-struct ZzTable {
-  uint8_t v[64];
-  constexpr ZzTable() : v{} {
-    constexpr uint8_t zz[64] = MYYUV_ZIGZAG;
-    for (int i = 0; i < 64; i++) v[i] = zz[i];
-  }
-};
-constexpr ZzTable kZz{};
-constexpr const uint8_t* c_zz = kZz.v;
+// (c_zz, the zig-zag order as compile-time constants: huff_common.hpp's)
 __constant__ uint8_t c_zz_dev[64] = MYYUV_ZIGZAG;
 
 __device__ __forceinline__ void record_error(unsigned long long* err, uint64_t key, int code) {
@@ -383,6 +377,7 @@ struct DecodeGroup {
   uint32_t f, gbase, g0, g1, g;
   int p;
   bool live;
+  bool good;  // live, and the lane's chunk decoded without an error
 };
 __device__ __forceinline__ bool decode_group(const uint8_t* __restrict__ in, const uint32_t* __restrict__ in_size,
                                              uint32_t cap, const StreamDesc* __restrict__ desc,
@@ -561,6 +556,7 @@ __device__ __forceinline__ bool decode_group(const uint8_t* __restrict__ in, con
   D.g = g;
   D.p = p;
   D.live = live;
+  D.good = ok && code == 0;
   return !bad;
 }
 
@@ -1160,5 +1156,92 @@ template __global__ void k_decode_scaled<2>(const uint8_t*, const uint32_t*, uin
 template __global__ void k_decode_scaled<4>(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
                                             const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t,
                                             const QTables*, uint4*, uint8_t*, unsigned long long*);
+
+// ---- requantise -----------------------------------------------------------
+//
+// k_requant: the decoder half of the requantiser (include/myyuv_hip.h,
+// "Requantise").  Grid and decode are k_decode_idct's: one wave per 64-block
+// group (blockIdx.x) of frame blockIdx.y, decode_group unchanged; a block with
+// a table that is not "regular" goes through the coefficient buffer as there
+// and is read back.  Then each lane rescales its block's 64 coefficients from
+// the source plane's table to the destination's in its nw[] registers
+// (requant.h; an all-zero row stays zero and is skipped) and writes K1's
+// hand-off for K2: the nonzero rows as natural-order quads, the row mask and
+// the block's info word, with msz and the class of the REQUANTISED block.
+//
+// Every live lane writes a mask and an info word, whatever the stream holds:
+// a lane whose chunk failed (D.good false: the partial symbols decode_regular
+// left in nw are dropped), and every lane of a frame whose header
+// k_scan_chain rejected, hands over an all-zero block (mask 0, msz 0, the
+// single class).  K2 indexes by these words, so it never sees what the
+// workspace held before; the error itself is in the shared error word.
+__global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_requant(const uint8_t* __restrict__ in,
+                                               const uint32_t* __restrict__ in_size,
+                                               uint32_t cap,
+                                               const StreamDesc* __restrict__ desc,
+                                               const uint32_t* __restrict__ local_off,
+                                               const uint32_t* __restrict__ tile_pre,
+                                               FrameGeom G, uint32_t tiles_p0,
+                                               uint32_t tiles_p1, const RequantTables* __restrict__ rt,
+                                               uint4* __restrict__ coef,
+                                               uint8_t* __restrict__ rmask,
+                                               uint32_t* __restrict__ binfo,
+                                               unsigned long long* __restrict__ err) {
+  __shared__ uint4 stq[kStageQuads + 1 + kGposQuads];
+  __shared__ float sqs[64], sqd[64];
+  const uint32_t lane = threadIdx.x;
+  if (lane == 0) stq[kStageQuads] = make_uint4(0u, 0u, 0u, 0u);  // (ordered by decode_group's barrier)
+  {
+    // the plane's two Q tables by LDS-DMA (landed by decode_group's final vmcnt wait)
+    const uint32_t t = blockIdx.x;
+    const int p = t >= tiles_p0 ? (t >= tiles_p0 + tiles_p1 ? 2 : 1) : 0;
+    __builtin_amdgcn_global_load_lds((const void*)&rt->qs[p][lane], (__attribute__((address_space(3))) void*)sqs, 4,
+                                     0, 0);
+    __builtin_amdgcn_global_load_lds((const void*)&rt->qd[p][lane], (__attribute__((address_space(3))) void*)sqd, 4,
+                                     0, 0);
+  }
+  DecodeGroup D;
+  CoefRegs R;
+  uint32_t(&nw)[32] = R.w;
+#pragma unroll
+  for (int w = 0; w < 32; w++) nw[w] = 0;
+  bool direct;
+  const bool frame_ok = decode_group(in, in_size, cap, desc, local_off, tile_pre, G, tiles_p0, tiles_p1, coef, err,
+                                     stq, D, nw, direct);
+  if (!D.live) return;
+  const uint32_t g = D.gbase + D.g;
+  const bool keep = frame_ok && D.good;
+  if (keep && direct) {  // decode_general wrote the block to coef (a table the reference never writes)
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      const uint4 v = coef[coef_quad(g, c)];
+      nw[4 * c] = v.x;
+      nw[4 * c + 1] = v.y;
+      nw[4 * c + 2] = v.z;
+      nw[4 * c + 3] = v.w;
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < 32; w++) nw[w] = keep ? nw[w] : 0u;
+  uint32_t m = 0;
+#pragma unroll
+  for (int c = 0; c < 8; c++) {
+    if ((nw[4 * c] | nw[4 * c + 1] | nw[4 * c + 2] | nw[4 * c + 3]) != 0u) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int n = 8 * c + 2 * k;  // coefficients n, n + 1 of the block
+        nw[4 * c + k] = myyuv_requant::requant_word(nw[4 * c + k], sqs[n], sqs[n + 1], sqd[n], sqd[n + 1]);
+      }
+    }
+    const bool nz = (nw[4 * c] | nw[4 * c + 1] | nw[4 * c + 2] | nw[4 * c + 3]) != 0u;
+    m |= nz ? 1u << c : 0u;
+    if (nz) coef[coef_quad(g, c)] = make_uint4(nw[4 * c], nw[4 * c + 1], nw[4 * c + 2], nw[4 * c + 3]);
+  }
+  int msz;
+  uint32_t cls;
+  block_class_msz(R, msz, cls);
+  rmask[g] = (uint8_t)m;
+  binfo[g] = binfo_word(m, (uint32_t)msz, cls, nw[0] & 0xFFFFu);
+}
 
 }  // namespace myyuv_gpu

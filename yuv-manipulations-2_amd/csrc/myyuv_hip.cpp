@@ -6,6 +6,7 @@
 //   decompress: parse -> scan -> K5 huff_decode -> K6 dequant_idct
 //   region:     parse -> scan -> decode_region (a rectangle's blocks only)
 //   scaled:     parse -> scan -> decode_scaled (every block, at 1/2, 1/4 or 1/8 size)
+//   requantise: parse -> scan -> requant (decode + rescale) -> K2 (+ overflow pass) -> K4
 // Every launch goes to one stream; nothing synchronises inside the
 // device-resident entry points, so frames pipeline back to back.
 // The context, the owners of its HIP resources and the entry points'
@@ -516,6 +517,68 @@ int launch_decompress_scaled(myyuv_hip_ctx* c, const FrameGeom& G, uint32_t deno
 }
 
 bool denom_ok(uint32_t denom) { return denom == 2 || denom == 4 || denom == 8; }
+
+// The requantiser's tables for (q_src, q_dst), on the device in stream order;
+// cached by the six quality bytes as set_qtables caches its triple.  The
+// compress / decompress tables (qt, qtd, q_cached, q_valid) are not touched.
+int set_requant_tables(myyuv_hip_ctx* c, const uint8_t qs[3], const uint8_t qd[3], hipStream_t s) {
+  uint8_t key[6];
+  std::memcpy(key, qs, 3);
+  std::memcpy(key + 3, qd, 3);
+  if (c->rq_valid && std::memcmp(c->rq_cached, key, 6) == 0 && c->rq_stream == s) return 0;
+  for (int p = 0; p < 3; p++) {
+    make_qtable(qs[p], p != 0, c->rq.qs[p]);
+    make_qtable(qd[p], p != 0, c->rq.qd[p]);
+  }
+  if (c->rqt.grow(sizeof(RequantTables))) return MYYUV_E_HIP;
+  // kernels queued on another stream may still read the old tables
+  if (c->rq_stream && c->rq_stream != s && hipStreamSynchronize(c->rq_stream) != hipSuccess) return MYYUV_E_HIP;
+  if (hipMemcpyAsync(c->rqt.p, &c->rq, sizeof(RequantTables), hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  c->rq_stream = s;
+  std::memcpy(c->rq_cached, key, 6);
+  c->rq_valid = true;
+  return 0;
+}
+
+// Requantise (include/myyuv_hip.h): stream f at d_in + f * cap_in (its size at
+// d_size_in[f]) -> stream f at d_out + f * cap_out, its size at d_size_out[f].
+// The scan as launch_decompress runs it; k_requant decodes every block,
+// rescales it and leaves K1's hand-off (coefficient quads, row masks, block
+// words); then the encoder from K2 on, as launch_compress runs it after K1.
+// work[0], K2's overflow count, is zeroed here as K1 would have.  No K1, no
+// fix kernel, no K6.  Workspace: reserve (the compress calls').
+int launch_requant(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_in, const uint32_t* d_size_in,
+                   uint32_t cap_in, void* d_out, uint32_t cap_out, uint32_t* d_size_out, hipStream_t s) {
+  const uint32_t nf = G.nframes;
+  const uint32_t ntiles = ceil_div(G.cum[3], kScanTile);
+  unsigned long long* err = c->err.as<unsigned long long>();
+  StreamDesc* desc = c->desc.as<StreamDesc>();
+  const uint8_t* in = static_cast<const uint8_t*>(d_in);
+  int e = 0;
+  ScanSrc SS;
+  for (int i = 0; i < 4; i++) SS.cum[i] = G.cum[i];
+  for (int p = 0; p < 3; p++) SS.pos[p] = 0;
+  e |= launch(c, MYYUV_K_SCAN, k_scan_chain, dim3(ntiles, nf), dim3(256), s, in, cap_in, SS, d_size_in, cap_in, G,
+              desc, c->loff.as<uint32_t>(), c->tiles.as<uint32_t>(), ntiles, c->status.as<unsigned long long>(),
+              next_epoch(c), err);
+  e |= hipMemsetAsync(c->work.p, 0, 4, s) != hipSuccess;
+  const uint32_t t0 = ceil_div(G.cum[1] - G.cum[0], kWave), t1 = ceil_div(G.cum[2] - G.cum[1], kWave),
+                 t2 = ceil_div(G.cum[3] - G.cum[2], kWave);
+  e |= launch(c, MYYUV_K_REQUANT, k_requant, dim3(t0 + t1 + t2, nf), dim3(kWave), s, in, d_size_in, cap_in,
+              (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, t0, t1,
+              c->rqt.as<const RequantTables>(), c->coef.as<uint4>(), c->rmask.as<uint8_t>(),
+              c->binfo.as<uint32_t>(), err);
+  e |= launch_huff_encode(c, G, s);
+  e |= launch(c, MYYUV_K_SCAN, k_tile_scan, dim3(nf), dim3(256), s, c->tinfo.as<uint32_t>(), G,
+              static_cast<uint8_t*>(d_out), cap_out, d_size_out, err);
+  const uint32_t W = k2_win(nf * G.tcum[3]);  // (K2's windows, as launch_compress)
+  e |= launch(c, MYYUV_K_COMPACT, k_stream_out, dim3(ceil_div(G.tcum[3] * nf, 8 * W) * 8 * W), dim3(256), s,
+              c->stage.as<const uint32_t>(), c->tinfo.as<const uint32_t>(), c->sizes.as<const uint8_t>(),
+              c->srcoff.as<const uint32_t>(), c->oslots.as<const uint32_t>(), G, static_cast<uint8_t*>(d_out),
+              cap_out, W);
+  return e ? MYYUV_E_HIP : 0;
+}
 
 // Host <-> device copies of the host-buffer entry points: direct async copies
 // from / into the caller's pageable buffers.  On this stack they run at the
@@ -1182,6 +1245,78 @@ int myyuv_gpu_dct_decompress_scaled_to_bmp(myyuv_hip_handle c, const uint8_t* pa
   }
   if (d2h(bmp_data, c->bmp.p, out_bytes, s)) return MYYUV_E_HIP;
   if (c->prof) drain_profile(c);
+  return 0;
+}
+
+// ---- requantise (defined in myyuv_hip.h) ------------------------------------
+int myyuv_gpu_dct_requantize(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                             const uint8_t q_src[3], const uint8_t q_dst[3], uint8_t* out, uint32_t cap,
+                             uint32_t* out_size, int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payload || !out || !out_size || !q_src || !q_dst) return MYYUV_E_ARG;
+  int e = check_q(q_src);
+  if (e) return e;
+  FrameGeom G;
+  if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G)) || (e = check_q(q_dst))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const uint32_t cap_in = (size + 3) & ~3u;
+  // the device writes into a buffer of the bound's size, so a result larger
+  // than the caller's `cap` is known by its size alone (as compress)
+  const uint32_t bound = myyuv_dct_payload_bound(w, h);
+  if ((e = reserve(c, G)) || (e = set_requant_tables(c, q_src, q_dst, s))) return e;
+  if (c->rqsrc.grow(cap_in) || c->payload.grow(bound) || c->psize.grow(8)) return MYYUV_E_HIP;
+  uint32_t* psz = c->psize.as<uint32_t>();  // [0] the source's size, [1] the result's
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (hipMemsetAsync(static_cast<uint8_t*>(c->rqsrc.p) + (cap_in - 4), 0, 4, s) != hipSuccess ||
+      h2d(c->rqsrc.p, payload, size, s) || hipMemcpyAsync(psz, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  if ((e = launch_requant(c, G, c->rqsrc.p, psz, cap_in, c->payload.p, bound, psz + 1, s))) return e;
+  uint32_t nout = 0;
+  if (hipMemcpyAsync(&nout, psz + 1, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return MYYUV_E_HIP;
+  if ((e = read_err(c, s, bad_block))) {  // (synchronises)
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  *out_size = nout;
+  if (nout > cap) return MYYUV_E_CAPACITY;
+  if (d2h(out, c->payload.p, nout, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+int myyuv_gpu_dct_requantize_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_payload_sizes,
+                                    uint32_t cap_in, uint32_t nframes, uint32_t w, uint32_t h,
+                                    const uint8_t q_src[3], const uint8_t q_dst[3], void* d_out, uint32_t cap_out,
+                                    uint32_t* d_out_sizes, void* stream) {
+  if (!c || !d_payload || !d_payload_sizes || !d_out || !d_out_sizes || !q_src || !q_dst) return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = check_q(q_src);
+  if (e || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes)) || (e = check_q(q_dst))) return e;
+  if (((uintptr_t)d_payload & 3) || ((uintptr_t)d_out & 3) || (nframes > 1 && ((cap_in | cap_out) & 3)))
+    return MYYUV_E_ARG;
+  {  // the two stream arrays must not overlap: K4 writes frame f while later frames are still being read
+    const uintptr_t a = (uintptr_t)d_payload, b = (uintptr_t)d_out;
+    const uint64_t na = (uint64_t)cap_in * nframes, nb = (uint64_t)cap_out * nframes;
+    if (a < b + nb && b < a + na) return MYYUV_E_ARG;
+  }
+  Entry en(c, stream);
+  // (as several launches past the kernels' 32-bit block numbers or the grid's 65,535 frames)
+  const uint32_t per = std::min(launch_frames(G, c->launch_blocks), 65535u);
+  FrameGeom GL = G;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve(c, GL)) ||
+      (e = set_requant_tables(c, q_src, q_dst, en.s)))
+    return e;
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GL.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
+    const uint8_t* src = static_cast<const uint8_t*>(d_payload) + (size_t)f0 * cap_in;
+    uint8_t* dst = static_cast<uint8_t*>(d_out) + (size_t)f0 * cap_out;
+    if ((e = launch_requant(c, GL, src, d_payload_sizes + f0, cap_in, dst, cap_out, d_out_sizes + f0, en.s)))
+      return e;
+  }
   return 0;
 }
 

@@ -22,10 +22,10 @@ CHROMA_NEAREST, CHROMA_LINEAR = 0, 1  # MYYUV_CHROMA_*
 
 KERNELS = ["fdct_quant", "huff_encode", "scan_tiles", "stream_out", "encode_tile", "huff_decode",
            "dequant_idct", "huff_encode_wide", "huff_encode_r16", "huff_encode_wave", "bmp_to_iyuv",
-           "fdct_fix", "iyuv_to_bmp", "decode_region", "decode_scaled"]
+           "fdct_fix", "iyuv_to_bmp", "decode_region", "decode_scaled", "requant"]
 # ids: MYYUV_K_* of include/myyuv_hip.h, in KERNELS order (tests/test_cabi.py checks both)
 (K_FDCT, K_HUFF_ENC, K_SCAN, K_COMPACT, K_ENCODE_TILE, K_HUFF_DEC, K_IDCT, K_HUFF_WIDE,
- K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP, K_REGION, K_SCALED) = range(len(KERNELS))
+ K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP, K_REGION, K_SCALED, K_REQUANT) = range(len(KERNELS))
 
 # the exported symbols include/myyuv_hip.h declares (checked by the CPU tests)
 EXPORTS = [
@@ -42,6 +42,7 @@ EXPORTS = [
     "myyuv_gpu_dct_decompress_region_to_bmp",
     "myyuv_gpu_dct_decompress_scaled", "myyuv_gpu_dct_decompress_scaled_device",
     "myyuv_gpu_dct_decompress_scaled_to_bmp",
+    "myyuv_gpu_dct_requantize", "myyuv_gpu_dct_requantize_device",
 ]
 
 _lib = None
@@ -133,6 +134,8 @@ def load():
     L.myyuv_gpu_dct_decompress_scaled.argtypes = [vp, u8p, u32, u32, u32, u8p, u32, u8p, i64p]
     L.myyuv_gpu_dct_decompress_scaled_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, u32, vp, vp]
     L.myyuv_gpu_dct_decompress_scaled_to_bmp.argtypes = [vp, u8p, u32, i32, i32, u8p, u32, u16, u32, u8p, i64p]
+    L.myyuv_gpu_dct_requantize.argtypes = [vp, u8p, u32, u32, u32, u8p, u8p, u8p, u32, ctypes.POINTER(u32), i64p]
+    L.myyuv_gpu_dct_requantize_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, u8p, vp, u32, vp, vp]
     L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -512,6 +515,41 @@ class Codec:
         if rc:
             raise CodecError(rc, bad.value)
         return out[:n].tobytes()
+
+    # -- requantise: a DCT stream re-encoded at another quality on its coefficients,
+    # no pixels in between (defined in include/myyuv_hip.h) --
+    def requantize(self, payload, w, h, q_src, q_dst):
+        """DCTYUV payload written at q_src -> the DCTYUV payload at q_dst, as bytes."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        out = np.empty(max(1, payload_bound(w, h)), np.uint8)
+        n = self.requantize_into(src, w, h, q_src, q_dst, out)
+        return out[:n].tobytes()
+
+    def requantize_into(self, payload, w, h, q_src, q_dst, out):
+        """requantize from / into the caller's C-contiguous uint8 arrays, which
+        must not overlap; returns the result's size.  `out` is sized by its
+        byte count (payload_bound(w, h) always fits; a short one fails with
+        E_CAPACITY)."""
+        src = _u8_array(payload, "payload")
+        dst = _u8_array(out, "out", writable=True)
+        size = ctypes.c_uint32(0)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_requantize(self._h, _u8(src), src.nbytes, w, h, _u8(_q(q_src)), _u8(_q(q_dst)),
+                                             _u8(dst), dst.nbytes, ctypes.byref(size), ctypes.byref(bad))
+        if rc:
+            raise CodecError(rc, bad.value)
+        return size.value
+
+    def requantize_device(self, d_payload, d_sizes, cap_in, nframes, w, h, q_src, q_dst, d_out, cap_out,
+                          d_out_sizes, stream=None):
+        """Device-resident batch: stream f at d_payload + f*cap_in (size
+        d_sizes[f]) -> stream f at d_out + f*cap_out, its size at
+        d_out_sizes[f] (device u32); asynchronous, errors through sync_status."""
+        rc = load().myyuv_gpu_dct_requantize_device(self._h, d_payload, d_sizes, cap_in, nframes, w, h,
+                                                    _u8(_q(q_src)), _u8(_q(q_dst)), d_out, cap_out, d_out_sizes,
+                                                    stream)
+        if rc:
+            raise CodecError(rc)
 
     # -- device-resident API (pointers are device addresses, e.g. torch data_ptr) --
     def reserve(self, w, h):
