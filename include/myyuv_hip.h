@@ -438,6 +438,84 @@ int myyuv_gpu_dct_requantize_device(myyuv_hip_handle h, const void* d_payload, c
                                     const uint8_t q_src[3], const uint8_t q_dst[3], void* d_out, uint32_t cap_out,
                                     uint32_t* d_out_sizes, void* stream);
 
+/* Transform: mirror, rotate or transpose a DCT stream on its coefficients
+ * (what jpegtran does for JPEG), optionally at another quality, without going
+ * through pixels.  Every block of the format stands alone, so each block is
+ * Huffman-decoded, moved inside the block (a transpose of the coefficients,
+ * sign changes for the mirrors), rescaled as Requantise rescales it, placed at
+ * its mirrored / transposed block position and encoded again.  No transform
+ * runs and no frame exists in HBM.  No reference program emits these bytes, so
+ * the definition is stated here, bit for bit.
+ *
+ * `op` is a 3-bit code: bit 0 = mirror x (mx), bit 1 = mirror y (my), bit 2 =
+ * swap (transpose first, then the mirrors): */
+#define MYYUV_XF_NONE 0       /* no change */
+#define MYYUV_XF_FLIP_H 1     /* mirror x */
+#define MYYUV_XF_FLIP_V 2     /* mirror y */
+#define MYYUV_XF_ROT180 3     /* both mirrors */
+#define MYYUV_XF_TRANSPOSE 4  /* swap: out[y][x] = in[x][y] */
+#define MYYUV_XF_ROT90 5      /* clockwise, numpy's rot90(a, -1): out[y][x] = in[H-1-x][y] */
+#define MYYUV_XF_ROT270 6     /* counter-clockwise: out[y][x] = in[x][W-1-y] */
+#define MYYUV_XF_TRANSVERSE 7 /* the anti-diagonal: out[y][x] = in[H-1-x][W-1-y] */
+#define MYYUV_XF_SWAPS(op) ((op) & 4)
+/* The output frame is height x width when MYYUV_XF_SWAPS(op), width x height
+ * otherwise; both satisfy the dimension checks whenever the source does, and
+ * the block, tile and unit counts of every plane are equal in both.
+ *
+ * For every plane p, the source block at (bx, by) of bw x bh blocks has the
+ * decoded coefficients z[u][v], natural order n = 8u + v, u the vertical
+ * frequency and v the horizontal; Qs and Qd are plane p's tables for q_src[p]
+ * and q_dst[p].
+ *   (u', v')    = swap ? (v, u) : (u, v)                        destination position
+ *   z1          = requant_coef(z[u][v], Qs[u][v], Qd[u'][v'])   Requantise's arithmetic, unchanged;
+ *                                                               the identity when the two entries are equal
+ *   z'[u'][v']  = clamp(s * z1, -1024, 1023)                    s = -1 iff (mx and v' odd) xor (my and u' odd)
+ *   (bx1, by1, bw1, bh1) = swap ? (by, bx, bh, bw) : (bx, by, bw, bh)
+ *   bx' = mx ? bw1 - 1 - bx1 : bx1,  by' = my ? bh1 - 1 - by1 : by1
+ *   the destination block is by' * bw1 + bx' of the same plane.
+ * The clamp after the sign matters for one value only: -(-1024) = 1024 does
+ * not fit the chunk format's 11 bits and becomes 1023.
+ * The output stream is the reference encoder's stream of the blocks z' in the
+ * destination's block order, laid out as for Requantise.
+ *
+ * Consequences:
+ *   - op = 0 is exactly myyuv_gpu_dct_requantize.
+ *   - With q_dst == q_src the three operations that do not swap change no
+ *     magnitude: they are involutions on every stream the encoder wrote
+ *     (applied twice, the source bytes come back), except for an AC
+ *     coefficient of -1024.
+ *   - The swapping operations are exact in the same sense for chroma always
+ *     (the chroma table is a symmetric matrix) and for luma if and only if its
+ *     table is symmetric (quality 100: all 1; quality 1: all 255).  Elsewhere a
+ *     luma coefficient is rescaled between Q[u][v] and Q[v][u], which costs
+ *     about what decode - rotate - encode costs in fidelity: there the gain of
+ *     a swapping operation is speed and the frame that never exists, not
+ *     fidelity.
+ *   - Decoded pixels of the result are NOT promised to equal the moved pixels
+ *     of the source's decode: the contract is bit for bit on coefficients.
+ *     (The inverse transform's basis is only almost symmetric, so on noise a
+ *     few pixels in ten thousand differ by one.)
+ *
+ * The in-block arithmetic and the block map are
+ * yuv-manipulations-2_amd/csrc/coef_xform.h, shared by the kernel and the host
+ * check.
+ * Checks and errors: op > 7 is MYYUV_E_ARG, together with the null-pointer
+ * checks.  Everything else, its order, *bad_block (in the SOURCE's block
+ * numbering), `cap` and MYYUV_E_CAPACITY are exactly myyuv_gpu_dct_requantize's,
+ * with `width` and `height` the source's.  Workspace: Requantise's, plus a
+ * scratch coefficient image (128 B per block) for streams with Huffman tables
+ * the encoder never writes. */
+int myyuv_gpu_dct_transform(myyuv_hip_handle h, const uint8_t* payload, uint32_t size, uint32_t width,
+                            uint32_t height, const uint8_t q_src[3], uint32_t op, const uint8_t q_dst[3],
+                            uint8_t* out, uint32_t cap, uint32_t* out_size, int64_t* bad_block);
+/* Device-resident batch: as myyuv_gpu_dct_requantize_device (same layout,
+ * alignment and overlap rules, same error reporting), every frame transformed
+ * by `op`. */
+int myyuv_gpu_dct_transform_device(myyuv_hip_handle h, const void* d_payload, const uint32_t* d_payload_sizes,
+                                   uint32_t cap_in, uint32_t nframes, uint32_t width, uint32_t height,
+                                   const uint8_t q_src[3], uint32_t op, const uint8_t q_dst[3], void* d_out,
+                                   uint32_t cap_out, uint32_t* d_out_sizes, void* stream);
+
 /* Host-buffer batches (many frames per call; §7 step 9:
  * transfers overlapped with the kernels).  The batch runs in chunks of up to
  * 8 frames through two device slots: chunk k's host -> device copies, chunk
@@ -507,7 +585,8 @@ int myyuv_hip_sync_status(myyuv_hip_handle h, void* stream, int64_t* bad_block);
 #define MYYUV_K_REGION 13    /* fused decoder of a rectangle of the frame (decode_region) */
 #define MYYUV_K_SCALED 14    /* fused decoder at 1/2, 1/4 or 1/8 size (decode_scaled) */
 #define MYYUV_K_REQUANT 15   /* decode + coefficient rescale of the requantiser (requant) */
-#define MYYUV_K_COUNT 16
+#define MYYUV_K_COEF_XF 16   /* decode + in-block move + rescale of the transform (coef_xform) */
+#define MYYUV_K_COUNT 17
 int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 /* As myyuv_hip_profile, but stamps only the kernels whose bit (1 << MYYUV_K_*)
  * is set in `mask` (0 disables): event stamping costs host and queue time per

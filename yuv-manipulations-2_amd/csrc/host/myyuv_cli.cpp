@@ -26,6 +26,10 @@
 // (requantise, include/myyuv_hip.h: no pixels in between; the qualities parse
 // and fill as -compress DCT's):
 //   myyuv_cli in.myyuv -requantize q [q [q]] -o out.myyuv
+// a compressed input mirrored, rotated or transposed on its coefficients
+// (transform, include/myyuv_hip.h; -q: re-encoded at those qualities on the
+// way, otherwise at its own):
+//   myyuv_cli in.myyuv -transform flip_h|flip_v|rot180|transpose|transverse|rot90|rot270 [-q q [q [q]]] -o out.myyuv
 // and, beyond the reference CLI, many frames per invocation (SURVEY.md §8f
 // row 2; frames of one geometry share batched kernel launches):
 //   myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IN.myyuv...
@@ -66,6 +70,9 @@ void usage() {
             << "      (-scale: a compressed image at that size, straight from its DCT coefficients)\n"
             << "  myyuv_cli IMAGE.myyuv -requantize Q [Q [Q]] -o OUT.myyuv\n"
             << "      (a compressed image at another quality, straight from its DCT coefficients)\n"
+            << "  myyuv_cli IMAGE.myyuv -transform flip_h|flip_v|rot180|transpose|transverse|rot90|rot270"
+               " [-q Q [Q [Q]]] -o OUT.myyuv\n"
+            << "      (a compressed image mirrored, rotated or transposed, straight from its DCT coefficients)\n"
             << "  myyuv_cli IMAGE.bmp -info\n"
             << "  myyuv_cli IMAGE.bmp -to_yuv IYUV -o OUT.myyuv\n"
             << "  myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IMAGE.myyuv...\n"
@@ -215,6 +222,51 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
       out = myyuvDCT::requantize_DCT_planar(yuv, {q[0], q[1], q[2]});
     });
     std::cout << "YUV DCT requantization (" << label << ") : " << ms << " ms\n";
+    out.dump(args[a]);
+    return 0;
+  }
+  if (cmd == "-transform") {  // OP [-q Q [Q [Q]]] -o OUT.myyuv: the qualities as -compress DCT's
+    if (!yuv.isCompressed()) {
+      std::cout << "Nothing to transform, image is not compressed (-transform needs DCT coefficients)\n";
+      return 1;
+    }
+    a++;
+    static const char* const names[8] = {nullptr,     "flip_h", "flip_v", "rot180",
+                                         "transpose", "rot90",  "rot270", "transverse"};
+    uint32_t op = 0;
+    for (uint32_t k = 1; k < 8 && a < args.size(); k++)
+      if (args[a] == names[k]) op = k;
+    if (!op) {
+      std::cout << "Invalid argument, -transform takes flip_h, flip_v, rot180, transpose, transverse, rot90 or "
+                   "rot270\n";
+      usage();
+      return 1;
+    }
+    a++;
+    const bool with_q = a < args.size() && args[a] == "-q";
+    std::vector<std::string> params;
+    if (with_q) a++;
+    while (a < args.size() && args[a] != "-o") params.push_back(args[a++]);
+    a++;
+    if (a >= args.size() || args.size() != a + 1 || (!with_q && !params.empty())) {
+      std::cout << "Invalid argument, last arguments must be `-o /path/to/new_image.myyuv`\n";
+      usage();
+      return 1;
+    }
+    std::string label = std::string(" ") + names[op] + " ";
+    for (const auto& p : params) label += p + " ";
+    myyuv::YUV out;
+    const float ms = elapsed_ms([&] {
+      uint8_t q[3];
+      if (with_q) {
+        dct_qualities(params, q);
+      } else {  // the image's own (transform_DCT_planar checks their count and range)
+        for (int p = 0; p < 3; p++)
+          q[p] = yuv.header.compression_params_size == 3 && yuv.compression_params ? yuv.compression_params[p] : 0;
+      }
+      out = myyuvDCT::transform_DCT_planar(yuv, op, {q[0], q[1], q[2]});
+    });
+    std::cout << "YUV DCT transform (" << label << ") : " << ms << " ms\n";
     out.dump(args[a]);
     return 0;
   }

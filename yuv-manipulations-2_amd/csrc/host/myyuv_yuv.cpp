@@ -639,10 +639,14 @@ myyuv::YUV decompress_DCT_planar_scaled(const myyuv::YUV& yuv, uint32_t denom) {
   return res;
 }
 
-// Requantise (include/myyuv_hip.h): the checks of decompress_DCT_planar_region
-// on the input, the new qualities' range as compress_DCT_planar checks it, and
-// compress_DCT_planar's header rewrite with the new quality bytes.
-myyuv::YUV requantize_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 3>& params) {
+namespace {
+
+// Requantise and transform (include/myyuv_hip.h): the checks of
+// decompress_DCT_planar_region on the input, the new qualities' range as
+// compress_DCT_planar checks it, and compress_DCT_planar's header rewrite with
+// the new quality bytes.  op < 0: requantise; otherwise MYYUV_XF_*, and the
+// header's width and height change places for a swapping operation.
+myyuv::YUV recode_DCT_planar(const myyuv::YUV& yuv, int op, const std::array<uint8_t, 3>& params) {
   using myyuv::YUV;
   if (yuv.getFormatGroup() != YUV::FormatGroup::PLANAR)
     throw std::runtime_error("Error decompressing: YUV must be planar");
@@ -659,11 +663,19 @@ myyuv::YUV requantize_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t
   std::vector<uint8_t> payload(myyuv_dct_payload_bound(w, h));
   uint32_t size = 0;
   int64_t bad = -1;
-  const int rc = myyuv_gpu_dct_requantize(t_codec.get(), yuv.data, yuv.header.data_size, w, h, yuv.compression_params,
-                                          params.data(), payload.data(), (uint32_t)payload.size(), &size, &bad);
+  const int rc =
+      op < 0 ? myyuv_gpu_dct_requantize(t_codec.get(), yuv.data, yuv.header.data_size, w, h, yuv.compression_params,
+                                        params.data(), payload.data(), (uint32_t)payload.size(), &size, &bad)
+             : myyuv_gpu_dct_transform(t_codec.get(), yuv.data, yuv.header.data_size, w, h, yuv.compression_params,
+                                       (uint32_t)op, params.data(), payload.data(), (uint32_t)payload.size(), &size,
+                                       &bad);
   if (rc) fail(rc);
   YUV res;
   res.header = yuv.header;
+  if (op >= 0 && MYYUV_XF_SWAPS(op)) {
+    res.header.width = h;
+    res.header.height = w;
+  }
   res.header.compression = YUV::Compressions::DCT;
   res.header.compression_params_size = 3;
   res.header.compression_params_pos = sizeof(myyuv::YUVHeader);
@@ -673,6 +685,17 @@ myyuv::YUV requantize_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t
   res.data = new uint8_t[size ? size : 1];
   std::memcpy(res.data, payload.data(), size);
   return res;
+}
+
+}  // namespace
+
+myyuv::YUV requantize_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 3>& params) {
+  return recode_DCT_planar(yuv, -1, params);
+}
+
+myyuv::YUV transform_DCT_planar(const myyuv::YUV& yuv, uint32_t op, const std::array<uint8_t, 3>& params) {
+  if (op > 7) throw std::runtime_error("Error transforming: unknown operation");
+  return recode_DCT_planar(yuv, (int)op, params);
 }
 
 // Many compressed frames per call. Each frame is checked as YUV::decompress

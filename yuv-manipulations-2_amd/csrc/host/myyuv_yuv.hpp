@@ -146,6 +146,11 @@ myyuv::YUV decompress_DCT_planar_scaled(const myyuv::YUV& yuv, uint32_t denom);
 // checks and messages for the input (an input that is not DCT-compressed is
 // refused); compress_DCT_planar's header with the three new quality bytes.
 myyuv::YUV requantize_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 3>& params);
+// Transform (include/myyuv_hip.h): the DCT-compressed frame mirrored, rotated
+// or transposed by `op` (MYYUV_XF_*) on its coefficients and re-encoded at the
+// qualities `params`, no pixels in between.  Checks, messages and header as
+// requantize_DCT_planar; width and height are swapped for a swapping operation.
+myyuv::YUV transform_DCT_planar(const myyuv::YUV& yuv, uint32_t op, const std::array<uint8_t, 3>& params);
 // Many frames per call: frames of one geometry share
 // one batched launch of every kernel; result i is compress_DCT_planar(*frames[i]).
 std::vector<myyuv::YUV> compress_DCT_planar_batch(const std::vector<const myyuv::YUV*>& frames,

@@ -39,6 +39,9 @@ __global__ void k_decode_scaled(const uint8_t*, const uint32_t*, uint32_t, const
 __global__ void k_requant(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
                           const uint32_t*, FrameGeom, uint32_t, uint32_t, const RequantTables*, uint4*, uint8_t*,
                           uint32_t*, unsigned long long*);
+__global__ void k_coef_xform(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
+                             const uint32_t*, FrameGeom, uint32_t, uint32_t, const RequantTables*, uint32_t, uint32_t,
+                             uint4*, uint4*, uint8_t*, uint32_t*, unsigned long long*);
 template <uint32_t W>
 __global__ void k_huff_encode(const uint4*, const uint32_t*, const uint4*, FrameGeom, uint32_t*, uint32_t*,
                               uint8_t*, uint32_t*, uint32_t*, uint32_t*);
@@ -188,6 +191,14 @@ struct myyuv_hip_ctx {
   hipStream_t rq_stream = nullptr;
   uint8_t rq_cached[6] = {0, 0, 0, 0, 0, 0};
   bool rq_valid = false;
+  // the transform's use of the same tables: qs held as the transposed block
+  // reads it (coef_xform.h xf_source_table) when rq_swap, which is part of the
+  // cache key; rq_eq: bit p set when plane p's two tables, so held, are equal.
+  // xfgen: the transform's scratch coefficient image for decode_general's
+  // blocks (source block order; grown by that path alone)
+  bool rq_swap = false;
+  uint32_t rq_eq = 0;
+  DevBuf xfgen;
   // profiling: the kernels' start/stop events until drain_profile reads
   // them; they are used again from launch to launch
   struct Stamp {

@@ -34,6 +34,7 @@
 //   words (the de-zig-zag of Huffman.cpp:148-153 is free) and the block is
 //   written as 8 quads of the codec_common.hpp layout that K6 reads.
 #include "codec_common.hpp"
+#include "coef_xform.h"
 #include "huff_common.hpp"
 #include "idct_scaled.h"
 #include "k_stream.hpp"
@@ -1232,6 +1233,111 @@ __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_requant(const uint8_t* _
         const int n = 8 * c + 2 * k;  // coefficients n, n + 1 of the block
         nw[4 * c + k] = myyuv_requant::requant_word(nw[4 * c + k], sqs[n], sqs[n + 1], sqd[n], sqd[n + 1]);
       }
+    }
+    const bool nz = (nw[4 * c] | nw[4 * c + 1] | nw[4 * c + 2] | nw[4 * c + 3]) != 0u;
+    m |= nz ? 1u << c : 0u;
+    if (nz) coef[coef_quad(g, c)] = make_uint4(nw[4 * c], nw[4 * c + 1], nw[4 * c + 2], nw[4 * c + 3]);
+  }
+  int msz;
+  uint32_t cls;
+  block_class_msz(R, msz, cls);
+  rmask[g] = (uint8_t)m;
+  binfo[g] = binfo_word(m, (uint32_t)msz, cls, nw[0] & 0xFFFFu);
+}
+
+// ---- transform ------------------------------------------------------------
+//
+// k_coef_xform: the decoder half of the coefficient-domain transform
+// (include/myyuv_hip.h, "Transform": flip, rotate, transpose).  Grid, decode
+// and hand-off are k_requant's, with two differences.
+//  - decode_general writes an irregular-table block at the SOURCE index of the
+//    buffer it is given, and that slot of the hand-off image is some other
+//    wave's destination: the decode gets a scratch image of its own (`gen`),
+//    and the block is read back from there.
+//  - Each lane moves its block inside its registers (coef_xform.h: the
+//    transpose with static register indices, the rescale where the plane's two
+//    tables differ, the mirrors' signs) and writes quads, mask and info word
+//    at the block's DESTINATION index, xf_dest_block of its position in the
+//    plane.  `rt->qs` is the source table as the transposed block reads it
+//    (xf_source_table, by the host); bit p of `eq`: plane p's two tables are
+//    equal, the rescale is the identity and is skipped.
+// The zero-block rule of k_requant holds at the destination: the map is a
+// bijection of the plane's blocks and every live lane writes, whatever the
+// stream holds, so every destination block has exactly one writer.
+// For a mirror the wave's 64 quads of a row land reversed inside one or two
+// 1 KiB runs of the image; for a swap every lane's quad lands in a run of its
+// own ("Transform", has the measurement).
+__global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_coef_xform(const uint8_t* __restrict__ in,
+                                                  const uint32_t* __restrict__ in_size,
+                                                  uint32_t cap,
+                                                  const StreamDesc* __restrict__ desc,
+                                                  const uint32_t* __restrict__ local_off,
+                                                  const uint32_t* __restrict__ tile_pre,
+                                                  FrameGeom G, uint32_t tiles_p0,
+                                                  uint32_t tiles_p1, const RequantTables* __restrict__ rt,
+                                                  uint32_t op, uint32_t eq,
+                                                  uint4* __restrict__ gen,
+                                                  uint4* __restrict__ coef,
+                                                  uint8_t* __restrict__ rmask,
+                                                  uint32_t* __restrict__ binfo,
+                                                  unsigned long long* __restrict__ err) {
+  __shared__ uint4 stq[kStageQuads + 1 + kGposQuads];
+  __shared__ float sqs[64], sqd[64];
+  const uint32_t lane = threadIdx.x;
+  if (lane == 0) stq[kStageQuads] = make_uint4(0u, 0u, 0u, 0u);  // (ordered by decode_group's barrier)
+  {
+    // the plane's two Q tables by LDS-DMA (landed by decode_group's final vmcnt wait)
+    const uint32_t t = blockIdx.x;
+    const int p = t >= tiles_p0 ? (t >= tiles_p0 + tiles_p1 ? 2 : 1) : 0;
+    __builtin_amdgcn_global_load_lds((const void*)&rt->qs[p][lane], (__attribute__((address_space(3))) void*)sqs, 4,
+                                     0, 0);
+    __builtin_amdgcn_global_load_lds((const void*)&rt->qd[p][lane], (__attribute__((address_space(3))) void*)sqd, 4,
+                                     0, 0);
+  }
+  DecodeGroup D;
+  CoefRegs R;
+  uint32_t(&nw)[32] = R.w;
+#pragma unroll
+  for (int w = 0; w < 32; w++) nw[w] = 0;
+  bool direct;
+  const bool frame_ok = decode_group(in, in_size, cap, desc, local_off, tile_pre, G, tiles_p0, tiles_p1, gen, err,
+                                     stq, D, nw, direct);
+  if (!D.live) return;
+  const bool keep = frame_ok && D.good;
+  if (keep && direct) {  // decode_general wrote the block to the scratch image, at the source index
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      const uint4 v = gen[coef_quad(D.gbase + D.g, c)];
+      nw[4 * c] = v.x;
+      nw[4 * c + 1] = v.y;
+      nw[4 * c + 2] = v.z;
+      nw[4 * c + 3] = v.w;
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < 32; w++) nw[w] = keep ? nw[w] : 0u;
+  // the destination block (plane fields by static index, as decode_group)
+  const int p = D.p;
+  const uint32_t cum_p = p == 0 ? G.cum[0] : (p == 1 ? G.cum[1] : G.cum[2]);
+  const uint32_t bw = p == 0 ? G.bw[0] : G.bw[1];                // (planes 1 and 2 have one shape)
+  const uint32_t bh = (p == 0 ? G.ph[0] : G.ph[1]) >> 3;
+  const uint32_t local = D.g - cum_p;
+  const uint32_t by = div_magic(local, p == 0 ? G.bmag[0] : G.bmag[1]);
+  const uint32_t g = D.gbase + cum_p + myyuv_xform::xf_dest_block(op, bw, bh, local - by * bw, by);
+  if (op & myyuv_xform::kSwap) {  // (wave-uniform)
+    uint32_t t[32];
+    myyuv_xform::xf_transpose(nw, t);
+#pragma unroll
+    for (int w = 0; w < 32; w++) nw[w] = t[w];
+  }
+  const bool mx = (op & myyuv_xform::kMirrorX) != 0, my = (op & myyuv_xform::kMirrorY) != 0;
+  const bool same = (eq >> p) & 1u;
+  uint32_t m = 0;
+#pragma unroll
+  for (int c = 0; c < 8; c++) {
+    if ((nw[4 * c] | nw[4 * c + 1] | nw[4 * c + 2] | nw[4 * c + 3]) != 0u) {
+      if (!same) myyuv_xform::xf_rescale_row(nw, c, sqs + 8 * c, sqd + 8 * c);
+      myyuv_xform::xf_sign_row(nw, c, mx, my);
     }
     const bool nz = (nw[4 * c] | nw[4 * c + 1] | nw[4 * c + 2] | nw[4 * c + 3]) != 0u;
     m |= nz ? 1u << c : 0u;

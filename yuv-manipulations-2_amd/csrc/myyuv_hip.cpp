@@ -7,6 +7,7 @@
 //   region:     parse -> scan -> decode_region (a rectangle's blocks only)
 //   scaled:     parse -> scan -> decode_scaled (every block, at 1/2, 1/4 or 1/8 size)
 //   requantise: parse -> scan -> requant (decode + rescale) -> K2 (+ overflow pass) -> K4
+//   transform:  parse -> scan -> coef_xform (decode + move + rescale) -> K2 (+ overflow pass) -> K4
 // Every launch goes to one stream; nothing synchronises inside the
 // device-resident entry points, so frames pipeline back to back.
 // The context, the owners of its HIP resources and the entry points'
@@ -18,6 +19,7 @@
 
 #include "host_ctx.hpp"
 // (after the HIP runtime header)
+#include "coef_xform.h"
 #include "fdct_bfly.h"
 
 #ifndef MYYUV_R16_BATCH
@@ -521,15 +523,25 @@ bool denom_ok(uint32_t denom) { return denom == 2 || denom == 4 || denom == 8; }
 // The requantiser's tables for (q_src, q_dst), on the device in stream order;
 // cached by the six quality bytes as set_qtables caches its triple.  The
 // compress / decompress tables (qt, qtd, q_cached, q_valid) are not touched.
-int set_requant_tables(myyuv_hip_ctx* c, const uint8_t qs[3], const uint8_t qd[3], hipStream_t s) {
+// swap (the transform's transposing operations): qs is held as the transposed
+// block reads it, qs[8u' + v'] = Qs[8v' + u'] (coef_xform.h xf_source_table).
+int set_requant_tables(myyuv_hip_ctx* c, const uint8_t qs[3], const uint8_t qd[3], hipStream_t s,
+                       bool swap = false) {
   uint8_t key[6];
   std::memcpy(key, qs, 3);
   std::memcpy(key + 3, qd, 3);
-  if (c->rq_valid && std::memcmp(c->rq_cached, key, 6) == 0 && c->rq_stream == s) return 0;
+  if (c->rq_valid && std::memcmp(c->rq_cached, key, 6) == 0 && c->rq_swap == swap && c->rq_stream == s)
+    return 0;
+  c->rq_valid = false;  // (until the new tables are queued)
+  c->rq_eq = 0;
   for (int p = 0; p < 3; p++) {
-    make_qtable(qs[p], p != 0, c->rq.qs[p]);
+    float t[64];
+    make_qtable(qs[p], p != 0, t);
+    myyuv_xform::xf_source_table(swap ? myyuv_xform::kSwap : 0u, t, c->rq.qs[p]);
     make_qtable(qd[p], p != 0, c->rq.qd[p]);
+    if (std::memcmp(c->rq.qs[p], c->rq.qd[p], sizeof(t)) == 0) c->rq_eq |= 1u << p;
   }
+  c->rq_swap = swap;
   if (c->rqt.grow(sizeof(RequantTables))) return MYYUV_E_HIP;
   // kernels queued on another stream may still read the old tables
   if (c->rq_stream && c->rq_stream != s && hipStreamSynchronize(c->rq_stream) != hipSuccess) return MYYUV_E_HIP;
@@ -541,15 +553,21 @@ int set_requant_tables(myyuv_hip_ctx* c, const uint8_t qs[3], const uint8_t qd[3
   return 0;
 }
 
-// Requantise (include/myyuv_hip.h): stream f at d_in + f * cap_in (its size at
-// d_size_in[f]) -> stream f at d_out + f * cap_out, its size at d_size_out[f].
-// The scan as launch_decompress runs it; k_requant decodes every block,
-// rescales it and leaves K1's hand-off (coefficient quads, row masks, block
-// words); then the encoder from K2 on, as launch_compress runs it after K1.
-// work[0], K2's overflow count, is zeroed here as K1 would have.  No K1, no
-// fix kernel, no K6.  Workspace: reserve (the compress calls').
-int launch_requant(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_in, const uint32_t* d_size_in,
-                   uint32_t cap_in, void* d_out, uint32_t cap_out, uint32_t* d_size_out, hipStream_t s) {
+// Requantise and transform (include/myyuv_hip.h): stream f at d_in + f * cap_in
+// (its size at d_size_in[f]) -> stream f at d_out + f * cap_out, its size at
+// d_size_out[f].  The scan as launch_decompress runs it; k_requant (op < 0) or
+// k_coef_xform decodes every block, rescales (and moves) it and leaves K1's
+// hand-off (coefficient quads, row masks, block words); then the encoder from
+// K2 on, as launch_compress runs it after K1.  work[0], K2's overflow count, is
+// zeroed here as K1 would have.  No K1, no fix kernel, no K6.  Workspace:
+// reserve (the compress calls'), and for the transform reserve_xform.
+// G is the source frame's geometry (the scan and the decode), Gd the
+// destination's (the encoder and the writer): the same batch, and the same
+// block, tile and unit counts per plane; they differ after a swap, in the
+// planes' widths.
+int launch_recode(myyuv_hip_ctx* c, const FrameGeom& G, const FrameGeom& Gd, int op, const void* d_in,
+                  const uint32_t* d_size_in, uint32_t cap_in, void* d_out, uint32_t cap_out, uint32_t* d_size_out,
+                  hipStream_t s) {
   const uint32_t nf = G.nframes;
   const uint32_t ntiles = ceil_div(G.cum[3], kScanTile);
   unsigned long long* err = c->err.as<unsigned long long>();
@@ -565,19 +583,58 @@ int launch_requant(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_in, const
   e |= hipMemsetAsync(c->work.p, 0, 4, s) != hipSuccess;
   const uint32_t t0 = ceil_div(G.cum[1] - G.cum[0], kWave), t1 = ceil_div(G.cum[2] - G.cum[1], kWave),
                  t2 = ceil_div(G.cum[3] - G.cum[2], kWave);
-  e |= launch(c, MYYUV_K_REQUANT, k_requant, dim3(t0 + t1 + t2, nf), dim3(kWave), s, in, d_size_in, cap_in,
-              (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, t0, t1,
-              c->rqt.as<const RequantTables>(), c->coef.as<uint4>(), c->rmask.as<uint8_t>(),
-              c->binfo.as<uint32_t>(), err);
-  e |= launch_huff_encode(c, G, s);
-  e |= launch(c, MYYUV_K_SCAN, k_tile_scan, dim3(nf), dim3(256), s, c->tinfo.as<uint32_t>(), G,
+  if (op < 0)
+    e |= launch(c, MYYUV_K_REQUANT, k_requant, dim3(t0 + t1 + t2, nf), dim3(kWave), s, in, d_size_in, cap_in,
+                (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, t0, t1,
+                c->rqt.as<const RequantTables>(), c->coef.as<uint4>(), c->rmask.as<uint8_t>(),
+                c->binfo.as<uint32_t>(), err);
+  else
+    e |= launch(c, MYYUV_K_COEF_XF, k_coef_xform, dim3(t0 + t1 + t2, nf), dim3(kWave), s, in, d_size_in, cap_in,
+                (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, t0, t1,
+                c->rqt.as<const RequantTables>(), (uint32_t)op, c->rq_eq, c->xfgen.as<uint4>(), c->coef.as<uint4>(),
+                c->rmask.as<uint8_t>(), c->binfo.as<uint32_t>(), err);
+  e |= launch_huff_encode(c, Gd, s);
+  e |= launch(c, MYYUV_K_SCAN, k_tile_scan, dim3(nf), dim3(256), s, c->tinfo.as<uint32_t>(), Gd,
               static_cast<uint8_t*>(d_out), cap_out, d_size_out, err);
-  const uint32_t W = k2_win(nf * G.tcum[3]);  // (K2's windows, as launch_compress)
-  e |= launch(c, MYYUV_K_COMPACT, k_stream_out, dim3(ceil_div(G.tcum[3] * nf, 8 * W) * 8 * W), dim3(256), s,
+  const uint32_t W = k2_win(nf * Gd.tcum[3]);  // (K2's windows, as launch_compress)
+  e |= launch(c, MYYUV_K_COMPACT, k_stream_out, dim3(ceil_div(Gd.tcum[3] * nf, 8 * W) * 8 * W), dim3(256), s,
               c->stage.as<const uint32_t>(), c->tinfo.as<const uint32_t>(), c->sizes.as<const uint8_t>(),
-              c->srcoff.as<const uint32_t>(), c->oslots.as<const uint32_t>(), G, static_cast<uint8_t*>(d_out),
+              c->srcoff.as<const uint32_t>(), c->oslots.as<const uint32_t>(), Gd, static_cast<uint8_t*>(d_out),
               cap_out, W);
   return e ? MYYUV_E_HIP : 0;
+}
+
+int launch_requant(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_in, const uint32_t* d_size_in,
+                   uint32_t cap_in, void* d_out, uint32_t cap_out, uint32_t* d_size_out, hipStream_t s) {
+  return launch_recode(c, G, G, -1, d_in, d_size_in, cap_in, d_out, cap_out, d_size_out, s);
+}
+
+// Transform (include/myyuv_hip.h): op is MYYUV_XF_*, Gd the geometry of the
+// H x W frame after a swap (G itself otherwise), with G's batch.
+int launch_coef_xform(myyuv_hip_ctx* c, const FrameGeom& G, const FrameGeom& Gd, uint32_t op, const void* d_in,
+                      const uint32_t* d_size_in, uint32_t cap_in, void* d_out, uint32_t cap_out,
+                      uint32_t* d_size_out, hipStream_t s) {
+  return launch_recode(c, G, Gd, (int)op, d_in, d_size_in, cap_in, d_out, cap_out, d_size_out, s);
+}
+
+// The transform's scratch coefficient image (decode_general's blocks, in
+// source order: the hand-off image is written in destination order by other
+// waves meanwhile), sized as reserve sizes the hand-off image.
+int reserve_xform(myyuv_hip_ctx* c, const FrameGeom& G) {
+  const uint32_t nwaves = ceil_div(G.cum[3] * G.nframes, kWave);
+  return c->xfgen.grow((size_t)nwaves * kCoefQuadsPerWave * 16) ? MYYUV_E_HIP : 0;
+}
+
+// The destination geometry of `op` on a w x h frame whose geometry is G, with
+// G's batch and launch base.
+int xform_geom(const FrameGeom& G, uint32_t w, uint32_t h, uint32_t op, FrameGeom& Gd) {
+  Gd = G;
+  if (!MYYUV_XF_SWAPS(op)) return 0;
+  const int e = make_geom(h, w, Gd);
+  if (e) return e;
+  Gd.nframes = G.nframes;
+  Gd.fbase = G.fbase;
+  return 0;
 }
 
 // Host <-> device copies of the host-buffer entry points: direct async copies
@@ -1248,30 +1305,38 @@ int myyuv_gpu_dct_decompress_scaled_to_bmp(myyuv_hip_handle c, const uint8_t* pa
   return 0;
 }
 
-// ---- requantise (defined in myyuv_hip.h) ------------------------------------
-int myyuv_gpu_dct_requantize(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
-                             const uint8_t q_src[3], const uint8_t q_dst[3], uint8_t* out, uint32_t cap,
-                             uint32_t* out_size, int64_t* bad_block) {
+// ---- requantise and transform (defined in myyuv_hip.h) ----------------------
+namespace {
+
+// Both host-buffer calls; op < 0: requantise.
+int recode_host(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                const uint8_t q_src[3], int op, const uint8_t q_dst[3], uint8_t* out, uint32_t cap,
+                uint32_t* out_size, int64_t* bad_block) {
   if (bad_block) *bad_block = -1;
-  if (!c || !payload || !out || !out_size || !q_src || !q_dst) return MYYUV_E_ARG;
+  if (!c || !payload || !out || !out_size || !q_src || !q_dst || op > 7) return MYYUV_E_ARG;
   int e = check_q(q_src);
   if (e) return e;
-  FrameGeom G;
+  FrameGeom G, Gd;
   if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G)) || (e = check_q(q_dst))) return e;
+  if (op >= 0 && (e = xform_geom(G, w, h, (uint32_t)op, Gd))) return e;
   Entry en(c);
   hipStream_t s = en.s;
   const uint32_t cap_in = (size + 3) & ~3u;
   // the device writes into a buffer of the bound's size, so a result larger
   // than the caller's `cap` is known by its size alone (as compress)
   const uint32_t bound = myyuv_dct_payload_bound(w, h);
-  if ((e = reserve(c, G)) || (e = set_requant_tables(c, q_src, q_dst, s))) return e;
+  if ((e = reserve(c, G)) || (op >= 0 && (e = reserve_xform(c, G))) ||
+      (e = set_requant_tables(c, q_src, q_dst, s, op >= 0 && MYYUV_XF_SWAPS(op))))
+    return e;
   if (c->rqsrc.grow(cap_in) || c->payload.grow(bound) || c->psize.grow(8)) return MYYUV_E_HIP;
   uint32_t* psz = c->psize.as<uint32_t>();  // [0] the source's size, [1] the result's
   if (reset_err(c, s)) return MYYUV_E_HIP;
   if (hipMemsetAsync(static_cast<uint8_t*>(c->rqsrc.p) + (cap_in - 4), 0, 4, s) != hipSuccess ||
       h2d(c->rqsrc.p, payload, size, s) || hipMemcpyAsync(psz, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
     return MYYUV_E_HIP;
-  if ((e = launch_requant(c, G, c->rqsrc.p, psz, cap_in, c->payload.p, bound, psz + 1, s))) return e;
+  e = op < 0 ? launch_requant(c, G, c->rqsrc.p, psz, cap_in, c->payload.p, bound, psz + 1, s)
+             : launch_coef_xform(c, G, Gd, (uint32_t)op, c->rqsrc.p, psz, cap_in, c->payload.p, bound, psz + 1, s);
+  if (e) return e;
   uint32_t nout = 0;
   if (hipMemcpyAsync(&nout, psz + 1, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return MYYUV_E_HIP;
   if ((e = read_err(c, s, bad_block))) {  // (synchronises)
@@ -1286,11 +1351,12 @@ int myyuv_gpu_dct_requantize(myyuv_hip_handle c, const uint8_t* payload, uint32_
   return 0;
 }
 
-int myyuv_gpu_dct_requantize_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_payload_sizes,
-                                    uint32_t cap_in, uint32_t nframes, uint32_t w, uint32_t h,
-                                    const uint8_t q_src[3], const uint8_t q_dst[3], void* d_out, uint32_t cap_out,
-                                    uint32_t* d_out_sizes, void* stream) {
-  if (!c || !d_payload || !d_payload_sizes || !d_out || !d_out_sizes || !q_src || !q_dst) return MYYUV_E_ARG;
+// Both device-resident batches; op < 0: requantise.
+int recode_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_payload_sizes, uint32_t cap_in,
+                  uint32_t nframes, uint32_t w, uint32_t h, const uint8_t q_src[3], int op, const uint8_t q_dst[3],
+                  void* d_out, uint32_t cap_out, uint32_t* d_out_sizes, void* stream) {
+  if (!c || !d_payload || !d_payload_sizes || !d_out || !d_out_sizes || !q_src || !q_dst || op > 7)
+    return MYYUV_E_ARG;
   FrameGeom G;
   int e = check_q(q_src);
   if (e || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes)) || (e = check_q(q_dst))) return e;
@@ -1304,9 +1370,10 @@ int myyuv_gpu_dct_requantize_device(myyuv_hip_handle c, const void* d_payload, c
   Entry en(c, stream);
   // (as several launches past the kernels' 32-bit block numbers or the grid's 65,535 frames)
   const uint32_t per = std::min(launch_frames(G, c->launch_blocks), 65535u);
-  FrameGeom GL = G;
+  FrameGeom GL = G, GD;
   if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve(c, GL)) ||
-      (e = set_requant_tables(c, q_src, q_dst, en.s)))
+      (op >= 0 && (e = reserve_xform(c, GL))) ||
+      (e = set_requant_tables(c, q_src, q_dst, en.s, op >= 0 && MYYUV_XF_SWAPS(op))))
     return e;
   for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
     GL = G;
@@ -1314,10 +1381,46 @@ int myyuv_gpu_dct_requantize_device(myyuv_hip_handle c, const void* d_payload, c
     if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
     const uint8_t* src = static_cast<const uint8_t*>(d_payload) + (size_t)f0 * cap_in;
     uint8_t* dst = static_cast<uint8_t*>(d_out) + (size_t)f0 * cap_out;
-    if ((e = launch_requant(c, GL, src, d_payload_sizes + f0, cap_in, dst, cap_out, d_out_sizes + f0, en.s)))
-      return e;
+    if (op < 0)
+      e = launch_requant(c, GL, src, d_payload_sizes + f0, cap_in, dst, cap_out, d_out_sizes + f0, en.s);
+    else if (!(e = xform_geom(GL, w, h, (uint32_t)op, GD)))
+      e = launch_coef_xform(c, GL, GD, (uint32_t)op, src, d_payload_sizes + f0, cap_in, dst, cap_out,
+                            d_out_sizes + f0, en.s);
+    if (e) return e;
   }
   return 0;
+}
+
+}  // namespace
+
+int myyuv_gpu_dct_requantize(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                             const uint8_t q_src[3], const uint8_t q_dst[3], uint8_t* out, uint32_t cap,
+                             uint32_t* out_size, int64_t* bad_block) {
+  return recode_host(c, payload, size, w, h, q_src, -1, q_dst, out, cap, out_size, bad_block);
+}
+
+int myyuv_gpu_dct_requantize_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_payload_sizes,
+                                    uint32_t cap_in, uint32_t nframes, uint32_t w, uint32_t h,
+                                    const uint8_t q_src[3], const uint8_t q_dst[3], void* d_out, uint32_t cap_out,
+                                    uint32_t* d_out_sizes, void* stream) {
+  return recode_device(c, d_payload, d_payload_sizes, cap_in, nframes, w, h, q_src, -1, q_dst, d_out, cap_out,
+                       d_out_sizes, stream);
+}
+
+int myyuv_gpu_dct_transform(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                            const uint8_t q_src[3], uint32_t op, const uint8_t q_dst[3], uint8_t* out, uint32_t cap,
+                            uint32_t* out_size, int64_t* bad_block) {
+  if (op > 7) op = 8;  // (any larger code: MYYUV_E_ARG below, whatever its low bits)
+  return recode_host(c, payload, size, w, h, q_src, (int)op, q_dst, out, cap, out_size, bad_block);
+}
+
+int myyuv_gpu_dct_transform_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_payload_sizes,
+                                   uint32_t cap_in, uint32_t nframes, uint32_t w, uint32_t h,
+                                   const uint8_t q_src[3], uint32_t op, const uint8_t q_dst[3], void* d_out,
+                                   uint32_t cap_out, uint32_t* d_out_sizes, void* stream) {
+  if (op > 7) op = 8;
+  return recode_device(c, d_payload, d_payload_sizes, cap_in, nframes, w, h, q_src, (int)op, q_dst, d_out, cap_out,
+                       d_out_sizes, stream);
 }
 
 // ---- host-buffer batches, pipelined ------------------

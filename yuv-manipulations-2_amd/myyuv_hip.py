@@ -22,10 +22,20 @@ CHROMA_NEAREST, CHROMA_LINEAR = 0, 1  # MYYUV_CHROMA_*
 
 KERNELS = ["fdct_quant", "huff_encode", "scan_tiles", "stream_out", "encode_tile", "huff_decode",
            "dequant_idct", "huff_encode_wide", "huff_encode_r16", "huff_encode_wave", "bmp_to_iyuv",
-           "fdct_fix", "iyuv_to_bmp", "decode_region", "decode_scaled", "requant"]
+           "fdct_fix", "iyuv_to_bmp", "decode_region", "decode_scaled", "requant", "coef_xform"]
 # ids: MYYUV_K_* of include/myyuv_hip.h, in KERNELS order (tests/test_cabi.py checks both)
 (K_FDCT, K_HUFF_ENC, K_SCAN, K_COMPACT, K_ENCODE_TILE, K_HUFF_DEC, K_IDCT, K_HUFF_WIDE,
- K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP, K_REGION, K_SCALED, K_REQUANT) = range(len(KERNELS))
+ K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP, K_REGION, K_SCALED, K_REQUANT,
+ K_COEF_XF) = range(len(KERNELS))
+# MYYUV_XF_*: bit 0 mirror x, bit 1 mirror y, bit 2 swap (transpose first, then the mirrors)
+(XF_NONE, XF_FLIP_H, XF_FLIP_V, XF_ROT180, XF_TRANSPOSE, XF_ROT90, XF_ROT270, XF_TRANSVERSE) = range(8)
+XF_NAMES = {"none": 0, "flip_h": 1, "flip_v": 2, "rot180": 3, "transpose": 4, "rot90": 5, "rot270": 6,
+            "transverse": 7}
+
+
+def xf_swaps(op):
+    """MYYUV_XF_SWAPS: the output frame is height x width."""
+    return bool(op & 4)
 
 # the exported symbols include/myyuv_hip.h declares (checked by the CPU tests)
 EXPORTS = [
@@ -43,6 +53,7 @@ EXPORTS = [
     "myyuv_gpu_dct_decompress_scaled", "myyuv_gpu_dct_decompress_scaled_device",
     "myyuv_gpu_dct_decompress_scaled_to_bmp",
     "myyuv_gpu_dct_requantize", "myyuv_gpu_dct_requantize_device",
+    "myyuv_gpu_dct_transform", "myyuv_gpu_dct_transform_device",
 ]
 
 _lib = None
@@ -136,6 +147,9 @@ def load():
     L.myyuv_gpu_dct_decompress_scaled_to_bmp.argtypes = [vp, u8p, u32, i32, i32, u8p, u32, u16, u32, u8p, i64p]
     L.myyuv_gpu_dct_requantize.argtypes = [vp, u8p, u32, u32, u32, u8p, u8p, u8p, u32, ctypes.POINTER(u32), i64p]
     L.myyuv_gpu_dct_requantize_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, u8p, vp, u32, vp, vp]
+    L.myyuv_gpu_dct_transform.argtypes = [vp, u8p, u32, u32, u32, u8p, u32, u8p, u8p, u32, ctypes.POINTER(u32),
+                                          i64p]
+    L.myyuv_gpu_dct_transform_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, u32, u8p, vp, u32, vp, vp]
     L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -548,6 +562,39 @@ class Codec:
         rc = load().myyuv_gpu_dct_requantize_device(self._h, d_payload, d_sizes, cap_in, nframes, w, h,
                                                     _u8(_q(q_src)), _u8(_q(q_dst)), d_out, cap_out, d_out_sizes,
                                                     stream)
+        if rc:
+            raise CodecError(rc)
+
+    # -- transform: a DCT stream mirrored, rotated or transposed on its coefficients,
+    # optionally at another quality (defined in include/myyuv_hip.h) --
+    def transform(self, payload, w, h, q_src, op, q_dst=None):
+        """DCTYUV payload of a w x h frame written at q_src -> the payload of
+        the frame moved by `op` (XF_*; h x w when xf_swaps(op)) at q_dst
+        (default: q_src), as bytes."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        out = np.empty(max(1, payload_bound(w, h)), np.uint8)
+        n = self.transform_into(src, w, h, q_src, op, q_src if q_dst is None else q_dst, out)
+        return out[:n].tobytes()
+
+    def transform_into(self, payload, w, h, q_src, op, q_dst, out):
+        """transform from / into the caller's C-contiguous uint8 arrays, which
+        must not overlap; returns the result's size (requantize_into's rules)."""
+        src = _u8_array(payload, "payload")
+        dst = _u8_array(out, "out", writable=True)
+        size = ctypes.c_uint32(0)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_transform(self._h, _u8(src), src.nbytes, w, h, _u8(_q(q_src)), op, _u8(_q(q_dst)),
+                                            _u8(dst), dst.nbytes, ctypes.byref(size), ctypes.byref(bad))
+        if rc:
+            raise CodecError(rc, bad.value)
+        return size.value
+
+    def transform_device(self, d_payload, d_sizes, cap_in, nframes, w, h, q_src, op, q_dst, d_out, cap_out,
+                         d_out_sizes, stream=None):
+        """Device-resident batch, as requantize_device, every frame moved by `op`."""
+        rc = load().myyuv_gpu_dct_transform_device(self._h, d_payload, d_sizes, cap_in, nframes, w, h,
+                                                   _u8(_q(q_src)), op, _u8(_q(q_dst)), d_out, cap_out, d_out_sizes,
+                                                   stream)
         if rc:
             raise CodecError(rc)
 
