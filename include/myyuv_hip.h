@@ -516,6 +516,110 @@ int myyuv_gpu_dct_transform_device(myyuv_hip_handle h, const void* d_payload, co
                                    const uint8_t q_src[3], uint32_t op, const uint8_t q_dst[3], void* d_out,
                                    uint32_t cap_out, uint32_t* d_out_sizes, void* stream);
 
+/* Crop and join: cut a rectangle out of a DCT stream, or lay a grid of equally
+ * sized streams side by side as one, without leaving the compressed form
+ * (jpegtran -crop, and -drop in its useful form).  Every block of the format
+ * stands alone (see Requantise) and every chunk is byte-aligned with a u8 size,
+ * so both are exact byte gathers: nothing is Huffman-decoded, there is no
+ * arithmetic, and no quantisation table is read.  No reference program emits
+ * these bytes, so the definition is stated here, bit for bit.
+ *
+ * For plane p, d = 8 (Y) or 16 (U, V): luma pixels per block of the plane.  A
+ * source frame W x H has bw = W/d blocks per row of plane p; size_p[k] is the
+ * plane's size table and chunk_p[k] its chunk k: size_p[k] bytes at the
+ * exclusive prefix sum of the sizes inside the plane's content.
+ *
+ * Crop (rx, ry, rw, rh), in luma pixels, top-down: all multiples of 16, rw,
+ * rh > 0, rx+rw <= W, ry+rh <= H (no 32-bit wrap) — region decode's rules.
+ * The output is the DCTYUV stream of an rw x rh frame:
+ *   - plane p has (rw/d) * (rh/d) blocks;
+ *   - block (by', bx') of plane p, row-major, takes the size byte and the
+ *     chunk bytes of the source plane's block (ry/d + by') * bw + rx/d + bx',
+ *     verbatim;
+ *   - plane_size[3], nblocks and content_size are written as DCTYUV::dump
+ *     writes them (plane_size = 8 + nblocks + content_size, no slack).
+ *
+ * Join (cols, rows, tile_w, tile_h and cols * rows streams of tile_w x tile_h
+ * frames, tile t = ty * cols + tx): tile_w, tile_h multiples of 16, cols,
+ * rows >= 1.  The output is the stream of a (cols*tile_w) x (rows*tile_h)
+ * frame; with bw_t = tile_w/d, bh_t = tile_h/d:
+ *   - block (by', bx') of plane p is block (by' mod bh_t) * bw_t + (bx' mod
+ *     bw_t) of plane p of tile (by' div bh_t) * cols + bx' div bw_t, verbatim.
+ *
+ * Chunks are NOT examined.  Consequences:
+ *   - The crop of a whole frame returns the source stream's bytes when the
+ *     source is laid out as DCTYUV::dump lays it out (plane_size[p] == 8 +
+ *     nblocks + content_size, the sizes summing to content_size).  Slack the
+ *     source declares beyond that is not carried over.
+ *   - For a stream the reference encoder wrote, crop equals
+ *     compress(pixel-crop(frame)), and join equals compress(assembled frame) at
+ *     the tiles' quality, byte for byte.
+ *   - A malformed chunk is carried over unreported, as region decode does not
+ *     report one outside its rectangle.
+ *   - Cropping tile t's rectangle out of a join returns tile t's stream.
+ *   - There is no quality argument.  A join of tiles compressed at different
+ *     qualities is a valid stream that no single quality decodes correctly;
+ *     the C ABI cannot know and does not check.  The CLI and the C++ mirror
+ *     check it, from the containers' params.
+ *
+ * Checks and errors, in order:
+ *   1. the handle, pointer, stream-header and % 8 dimension checks of
+ *      myyuv_gpu_dct_decompress, in its order (`out` and `out_size` among the
+ *      pointers); there is no quality check.  Join needs cols, rows >= 1 and
+ *      cols * rows <= 65,535 here already (MYYUV_E_ARG): they say how many
+ *      streams there are;
+ *   2. the rectangle or the grid: MYYUV_E_ARG.  Join: also when cols*tile_w or
+ *      rows*tile_h wraps 32 bits, or when myyuv_gpu_dct_compress would refuse
+ *      the output frame for its size;
+ *   3. a source's stream-header error gives myyuv_gpu_dct_decompress's code,
+ *      *bad_block the batch-global index f * blocks_per_frame of that stream's
+ *      first block as the device batches report it (-1 for f = 0); for join f
+ *      is the tile index.  The lowest f wins;
+ *   4. a selected chunk that ends beyond its plane's declared content_size:
+ *      MYYUV_E_PLANE_CONTENT, reported exactly as region decode reports it:
+ *      *bad_block is the first block of the failing plane in the source's
+ *      batch-global numbering (-1 when that is block 0), the lowest one when
+ *      several fail.  Crop: an overrun outside the rectangle is not reported;
+ *   5. a result larger than `cap`: MYYUV_E_CAPACITY, *out_size the size needed
+ *      (as Requantise).  Nothing is written outside [out, out + cap);
+ *   6. `payload` (every tile) and `out` must not overlap: MYYUV_E_ARG.
+ * After an error of 3 or 4 the output bytes are unspecified, inside `cap`.
+ * The index map is yuv-manipulations-2_amd/csrc/stream_gather.h, shared by the
+ * kernels and the host check.
+ * Workspace: the scans (4 B per source block and 4 B per output block, plus
+ * tile words) and 1 B per output block; nothing of the 471 B per block the
+ * codec calls reserve.  The host-buffer forms copy the whole source stream(s)
+ * to the device and the result back. */
+int myyuv_gpu_dct_crop(myyuv_hip_handle h, const uint8_t* payload, uint32_t size, uint32_t width, uint32_t height,
+                       uint32_t rx, uint32_t ry, uint32_t rw, uint32_t rh, uint8_t* out, uint32_t cap,
+                       uint32_t* out_size, int64_t* bad_block);
+/* Device-resident batch, one rectangle for all frames: stream f at d_payload +
+ * f*cap_in (its size at d_payload_sizes[f], read inside min(size word,
+ * cap_in)) -> stream f at d_out + f*cap_out, its size at d_out_sizes[f];
+ * asynchronous on `stream` (NULL = the context's).  myyuv_gpu_dct_requantize_device's
+ * rules: d_payload and d_out 4-byte aligned, cap_in and cap_out multiples of 4
+ * when nframes > 1, the two arrays must not overlap (MYYUV_E_ARG, returned at
+ * once, after the dimension and rectangle checks).  Device-side errors come
+ * through myyuv_hip_sync_status: a source stream's with the batch-global
+ * block index, a frame larger than cap_out as MYYUV_E_CAPACITY (no block; it
+ * takes precedence; nothing of that frame but d_out_sizes[f] is written).  A
+ * frame with a source error does not disturb the others. */
+int myyuv_gpu_dct_crop_device(myyuv_hip_handle h, const void* d_payload, const uint32_t* d_payload_sizes,
+                              uint32_t cap_in, uint32_t nframes, uint32_t width, uint32_t height, uint32_t rx,
+                              uint32_t ry, uint32_t rw, uint32_t rh, void* d_out, uint32_t cap_out,
+                              uint32_t* d_out_sizes, void* stream);
+/* payloads[t] / sizes[t]: tile t's stream, t = ty * cols + tx. */
+int myyuv_gpu_dct_join(myyuv_hip_handle h, const uint8_t* const* payloads, const uint32_t* sizes, uint32_t cols,
+                       uint32_t rows, uint32_t tile_w, uint32_t tile_h, uint8_t* out, uint32_t cap,
+                       uint32_t* out_size, int64_t* bad_block);
+/* Device-resident form, one output frame per call: tile t at d_payload +
+ * t*cap_in (cap_in a multiple of 4 when cols * rows > 1), its size at
+ * d_payload_sizes[t] -> the stream at d_out (capacity cap_out), its size at
+ * *d_out_size.  Otherwise as myyuv_gpu_dct_crop_device. */
+int myyuv_gpu_dct_join_device(myyuv_hip_handle h, const void* d_payload, const uint32_t* d_payload_sizes,
+                              uint32_t cap_in, uint32_t cols, uint32_t rows, uint32_t tile_w, uint32_t tile_h,
+                              void* d_out, uint32_t cap_out, uint32_t* d_out_size, void* stream);
+
 /* Host-buffer batches (many frames per call; §7 step 9:
  * transfers overlapped with the kernels).  The batch runs in chunks of up to
  * 8 frames through two device slots: chunk k's host -> device copies, chunk
@@ -586,7 +690,14 @@ int myyuv_hip_sync_status(myyuv_hip_handle h, void* stream, int64_t* bad_block);
 #define MYYUV_K_SCALED 14    /* fused decoder at 1/2, 1/4 or 1/8 size (decode_scaled) */
 #define MYYUV_K_REQUANT 15   /* decode + coefficient rescale of the requantiser (requant) */
 #define MYYUV_K_COEF_XF 16   /* decode + in-block move + rescale of the transform (coef_xform) */
+/* MYYUV_K_COUNT is the length of the arrays myyuv_hip_kernel_stats fills.  It
+ * is part of that call's ABI (a caller built against this header passes
+ * arrays of exactly that length), so it no longer grows: ids from
+ * MYYUV_K_COUNT on are profiled like any other (their mask bits included) and
+ * read with myyuv_hip_kernel_stats_n, which takes the arrays' length. */
 #define MYYUV_K_COUNT 17
+#define MYYUV_K_GATHER 17    /* byte gather of crop and join, wave per run (stream_gather) */
+#define MYYUV_K_TOTAL 18     /* every id above is below this */
 int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 /* As myyuv_hip_profile, but stamps only the kernels whose bit (1 << MYYUV_K_*)
  * is set in `mask` (0 disables): event stamping costs host and queue time per
@@ -594,6 +705,9 @@ int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 int myyuv_hip_profile_kernels(myyuv_hip_handle h, uint32_t mask);
 int myyuv_hip_kernel_stats(myyuv_hip_handle h, double ms[MYYUV_K_COUNT],
                            int64_t launches[MYYUV_K_COUNT]);
+/* The same for the first min(n, MYYUV_K_TOTAL) ids; entries from
+ * MYYUV_K_TOTAL on, if any, are set to 0. */
+int myyuv_hip_kernel_stats_n(myyuv_hip_handle h, uint32_t n, double* ms, int64_t* launches);
 
 /* Block-level entry points for known-answer tests (device round trip of one
  * batch of blocks).  coef is zig-zag ordered int16[64] per block; the encoder

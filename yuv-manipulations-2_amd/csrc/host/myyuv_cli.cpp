@@ -30,6 +30,12 @@
 // (transform, include/myyuv_hip.h; -q: re-encoded at those qualities on the
 // way, otherwise at its own):
 //   myyuv_cli in.myyuv -transform flip_h|flip_v|rot180|transpose|transverse|rot90|rot270 [-q q [q [q]]] -o out.myyuv
+// a rectangle of a compressed input, still compressed, and a grid of
+// compressed tiles as one compressed image (crop and join, include/myyuv_hip.h:
+// byte gathers of the chunks, nothing decoded; -crop directly after the image
+// is this command, after -decompress or -to_bmp it is their option):
+//   myyuv_cli in.myyuv -crop X Y W H -o out.myyuv
+//   myyuv_cli -join COLS ROWS -o out.myyuv tile.myyuv...   (COLS * ROWS files, row-major)
 // and, beyond the reference CLI, many frames per invocation (SURVEY.md §8f
 // row 2; frames of one geometry share batched kernel launches):
 //   myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IN.myyuv...
@@ -73,6 +79,10 @@ void usage() {
             << "  myyuv_cli IMAGE.myyuv -transform flip_h|flip_v|rot180|transpose|transverse|rot90|rot270"
                " [-q Q [Q [Q]]] -o OUT.myyuv\n"
             << "      (a compressed image mirrored, rotated or transposed, straight from its DCT coefficients)\n"
+            << "  myyuv_cli IMAGE.myyuv -crop X Y W H -o OUT.myyuv\n"
+            << "      (a compressed image's rectangle, still compressed: its chunks, untouched)\n"
+            << "  myyuv_cli -join COLS ROWS -o OUT.myyuv TILE.myyuv...\n"
+            << "      (COLS x ROWS compressed tiles of one size and quality, row-major, as one compressed image)\n"
             << "  myyuv_cli IMAGE.bmp -info\n"
             << "  myyuv_cli IMAGE.bmp -to_yuv IYUV -o OUT.myyuv\n"
             << "  myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IMAGE.myyuv...\n"
@@ -268,6 +278,28 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     });
     std::cout << "YUV DCT transform (" << label << ") : " << ms << " ms\n";
     out.dump(args[a]);
+    return 0;
+  }
+  if (cmd == "-crop") {  // X Y W H -o OUT.myyuv: the rectangle, still compressed
+    if (!yuv.isCompressed()) {
+      std::cout << "Nothing to crop, image is not compressed (-crop keeps DCT chunks; use -decompress -crop)\n";
+      return 1;
+    }
+    uint32_t r[4] = {0, 0, 0, 0};
+    if (!parse_crop(args, a, r)) {
+      std::cout << kCropHelp;
+      usage();
+      return 1;
+    }
+    if (args.size() != a + 2 || args[a] != "-o") {
+      std::cout << "Invalid argument, last arguments must be `-o /path/to/new_image.myyuv`\n";
+      usage();
+      return 1;
+    }
+    myyuv::YUV out;
+    const float ms = elapsed_ms([&] { out = myyuvDCT::crop_DCT_planar(yuv, r[0], r[1], r[2], r[3]); });
+    std::cout << "YUV DCT crop (" << r[0] << " " << r[1] << " " << r[2] << " " << r[3] << ") : " << ms << " ms\n";
+    out.dump(args[a + 1]);
     return 0;
   }
   if (cmd == "-decompress") {
@@ -477,12 +509,58 @@ int run_batch(const std::vector<std::string>& args) {
   return 0;
 }
 
+// -join COLS ROWS -o OUT.myyuv TILE.myyuv...: COLS * ROWS compressed tiles of
+// one size and quality, row-major, as one compressed image
+int run_join(const std::vector<std::string>& args) {
+  auto number = [](const std::string& v, uint32_t& x) {
+    if (v.empty() || v.size() > 5 || v.find_first_not_of("0123456789") != std::string::npos) return false;
+    x = (uint32_t)std::stoul(v);
+    return x > 0;
+  };
+  uint32_t cols = 0, rows = 0;
+  if (args.size() < 4 || !number(args[2], cols) || !number(args[3], rows)) {
+    std::cout << "Invalid argument, -join must be followed by two numbers `COLS ROWS`\n";
+    usage();
+    return 1;
+  }
+  if (args.size() < 7 || args[4] != "-o") {
+    std::cout << "Invalid arguments. Expected -o OUT.myyuv followed by the tiles\n";
+    usage();
+    return 1;
+  }
+  if (args.size() - 6 != (size_t)cols * rows) {
+    std::cout << "Invalid arguments amount. " << (uint64_t)cols * rows << " tiles are required, " << args.size() - 6
+              << " given\n";
+    usage();
+    return 1;
+  }
+  std::vector<myyuv::YUV> in;
+  for (size_t i = 6; i < args.size(); i++) in.emplace_back(args[i]);
+  for (const auto& y : in)
+    if (!y.isCompressed()) {
+      std::cout << "Nothing to join, a tile is not compressed (-join keeps DCT chunks)\n";
+      return 1;
+    }
+  std::vector<const myyuv::YUV*> ptrs;
+  for (const auto& y : in) ptrs.push_back(&y);
+  myyuv::YUV out;
+  const float ms = elapsed_ms([&] { out = myyuvDCT::join_DCT_planar(ptrs, cols, rows); });
+  std::cout << "YUV DCT join (" << cols << " " << rows << ") : " << ms << " ms\n";
+  out.dump(args[5]);
+  return 0;
+}
+
 int run(int argc, char* argv[]) {
   if (argc <= 2) {
     usage();
     return 0;
   }
   const std::vector<std::string> args(argv, argv + argc);
+  if (args[1] == "-join") {
+    const int rc = run_join(args);
+    if (rc == 0) std::cout << "Success!\n";
+    return rc;
+  }
   if (args[1] == "-batch-compress" || args[1] == "-batch-decompress") {
     const int rc = run_batch(args);
     if (rc == 0) std::cout << "Success!\n";

@@ -698,6 +698,89 @@ myyuv::YUV transform_DCT_planar(const myyuv::YUV& yuv, uint32_t op, const std::a
   return recode_DCT_planar(yuv, (int)op, params);
 }
 
+namespace {
+
+// The input checks of decompress_DCT_planar_region, and the header of a
+// compressed w x h result that keeps the source's quality bytes.
+void check_dct_input(const myyuv::YUV& yuv) {
+  using myyuv::YUV;
+  if (yuv.getFormatGroup() != YUV::FormatGroup::PLANAR)
+    throw std::runtime_error("Error decompressing: YUV must be planar");
+  if (yuv.getCompression() != YUV::Compressions::DCT)
+    throw std::runtime_error("Error this decompression is unimplemented");
+  if (yuv.header.compression_params_size != 3 || !yuv.compression_params)
+    throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
+}
+
+myyuv::YUV gathered(const myyuv::YUV& like, uint32_t w, uint32_t h, const std::vector<uint8_t>& payload,
+                    uint32_t size) {
+  using myyuv::YUV;
+  YUV res;
+  res.header = like.header;
+  res.header.width = w;
+  res.header.height = h;
+  res.header.compression = YUV::Compressions::DCT;
+  res.header.compression_params_size = 3;
+  res.header.compression_params_pos = sizeof(myyuv::YUVHeader);
+  res.header.data_pos = sizeof(myyuv::YUVHeader) + 3;
+  res.header.data_size = size;
+  res.compression_params =
+      new uint8_t[3]{like.compression_params[0], like.compression_params[1], like.compression_params[2]};
+  res.data = new uint8_t[size ? size : 1];
+  std::memcpy(res.data, payload.data(), size);
+  return res;
+}
+
+}  // namespace
+
+// Crop (include/myyuv_hip.h): the rectangle of a compressed frame, still
+// compressed, with the source's params; the C ABI checks the rectangle.
+myyuv::YUV crop_DCT_planar(const myyuv::YUV& yuv, uint32_t x, uint32_t y, uint32_t w, uint32_t h) {
+  check_dct_input(yuv);
+  std::vector<uint8_t> payload((size_t)yuv.header.data_size + 36);  // (a part of the source never exceeds it)
+  uint32_t size = 0;
+  int64_t bad = -1;
+  const int rc = myyuv_gpu_dct_crop(t_codec.get(), yuv.data, yuv.header.data_size, yuv.header.width,
+                                    yuv.header.height, x, y, w, h, payload.data(), (uint32_t)payload.size(), &size,
+                                    &bad);
+  if (rc) fail(rc);
+  return gathered(yuv, w, h, payload, size);
+}
+
+// Join (include/myyuv_hip.h): cols x rows compressed tiles, row-major, as one
+// compressed frame.  The tiles' sizes, formats and params must be equal: a
+// stream of mixed qualities is one no single quality decodes.
+myyuv::YUV join_DCT_planar(const std::vector<const myyuv::YUV*>& tiles, uint32_t cols, uint32_t rows) {
+  if (cols == 0 || rows == 0 || (uint64_t)cols * rows != tiles.size())
+    throw std::runtime_error("Error joining: cols * rows tiles are required");
+  std::vector<const uint8_t*> ptrs;
+  std::vector<uint32_t> sizes;
+  uint64_t total = 36;
+  for (const myyuv::YUV* t : tiles) {
+    if (!t) throw std::runtime_error("Error joining: cols * rows tiles are required");
+    check_dct_input(*t);
+    const myyuv::YUV& a = *tiles[0];
+    if (t->header.width != a.header.width || t->header.height != a.header.height)
+      throw std::runtime_error("Error joining: tiles differ in size");
+    if (t->header.fourcc_format != a.header.fourcc_format)
+      throw std::runtime_error("Error joining: tiles differ in format");
+    if (std::memcmp(t->compression_params, a.compression_params, 3) != 0)
+      throw std::runtime_error("Error joining: tiles differ in compression params");
+    ptrs.push_back(t->data);
+    sizes.push_back(t->header.data_size);
+    total += t->header.data_size;
+  }
+  if (total > 0xFFFFFFF0ull) fail(MYYUV_E_ARG);
+  const uint32_t tw = tiles[0]->header.width, th = tiles[0]->header.height;
+  std::vector<uint8_t> payload((size_t)total);
+  uint32_t size = 0;
+  int64_t bad = -1;
+  const int rc = myyuv_gpu_dct_join(t_codec.get(), ptrs.data(), sizes.data(), cols, rows, tw, th, payload.data(),
+                                    (uint32_t)payload.size(), &size, &bad);
+  if (rc) fail(rc);
+  return gathered(*tiles[0], cols * tw, rows * th, payload, size);
+}
+
 // Many compressed frames per call. Each frame is checked as YUV::decompress
 // -> decompress_map[DCT][IYUV] -> decompress_DCT_planar would, in input order
 // (frames that are not DCT / IYUV, or fail a check, take that single-frame

@@ -151,6 +151,15 @@ myyuv::YUV requantize_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t
 // qualities `params`, no pixels in between.  Checks, messages and header as
 // requantize_DCT_planar; width and height are swapped for a swapping operation.
 myyuv::YUV transform_DCT_planar(const myyuv::YUV& yuv, uint32_t op, const std::array<uint8_t, 3>& params);
+// Crop (include/myyuv_hip.h): the w x h rectangle at (x, y) of a DCT-compressed
+// frame, still compressed: its blocks' chunk bytes, gathered on the GPU.
+// requantize_DCT_planar's checks on the input; compress_DCT_planar's header
+// with the new size and the source's quality bytes.
+myyuv::YUV crop_DCT_planar(const myyuv::YUV& yuv, uint32_t x, uint32_t y, uint32_t w, uint32_t h);
+// Join (include/myyuv_hip.h): cols x rows DCT-compressed tiles (row-major) as
+// one compressed frame.  Throws when the tiles' sizes, formats or params
+// differ, or their count is not cols * rows.
+myyuv::YUV join_DCT_planar(const std::vector<const myyuv::YUV*>& tiles, uint32_t cols, uint32_t rows);
 // Many frames per call: frames of one geometry share
 // one batched launch of every kernel; result i is compress_DCT_planar(*frames[i]).
 std::vector<myyuv::YUV> compress_DCT_planar_batch(const std::vector<const myyuv::YUV*>& frames,

@@ -18,6 +18,7 @@
 #include "k_chain.hpp"
 #include "k_stream.hpp"
 #include "myyuv_hip.h"
+#include "stream_gather.h"
 
 namespace myyuv_gpu {
 __global__ void k_fdct_quant(const uint8_t*, FrameGeom, const QTables*, uint4*, uint8_t*, uint32_t*, uint4*,
@@ -64,6 +65,14 @@ __global__ void k_stream_out(const uint32_t*, const uint32_t*, const uint8_t*, c
 __global__ void k_huff_decode(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
                               const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t,
                               uint4*, uint8_t*, unsigned long long*);
+__global__ void k_gather_sizes(const uint8_t*, uint32_t, const StreamDesc*, myyuv_gather::GatherMap, uint8_t*);
+__global__ void k_gather_heads(const uint32_t*, const uint32_t*, myyuv_gather::GatherMap, uint8_t*, uint32_t,
+                               uint32_t, uint32_t*, unsigned long long*);
+__global__ void k_gather_check(const uint8_t*, uint32_t, const StreamDesc*, const uint32_t*, const uint32_t*,
+                               myyuv_gather::GatherMap, uint32_t, unsigned long long*);
+__global__ void k_stream_gather(const uint8_t*, uint32_t, const StreamDesc*, const uint32_t*, const uint32_t*,
+                                const uint8_t*, const uint32_t*, const uint32_t*, myyuv_gather::GatherMap, uint32_t,
+                                uint8_t*, uint32_t, unsigned long long*);
 template <int BPP>
 __global__ void k_bmp_to_iyuv(const uint8_t*, uint32_t, uint32_t, uint32_t, uint8_t*);
 template <int BPP, int LINEAR>
@@ -199,6 +208,10 @@ struct myyuv_hip_ctx {
   bool rq_swap = false;
   uint32_t rq_eq = 0;
   DevBuf xfgen;
+  // crop and join: the output blocks' size bytes in destination order, and the
+  // destination scan's group offsets and tile prefixes (the source scan's are
+  // loff / tiles; the status words serve both scans, one after the other)
+  DevBuf gsz, gloff, gtiles;
   // profiling: the kernels' start/stop events until drain_profile reads
   // them; they are used again from launch to launch
   struct Stamp {
@@ -207,8 +220,8 @@ struct myyuv_hip_ctx {
   };
   uint32_t prof = 0;  // bit k: stamp kernel id k
   uint32_t skip = 0;  // diagnostic: bit k: do not launch kernel id k (myyuv_debug_skip_kernels)
-  double ms[MYYUV_K_COUNT] = {};
-  int64_t launches[MYYUV_K_COUNT] = {};
+  double ms[MYYUV_K_TOTAL] = {};
+  int64_t launches[MYYUV_K_TOTAL] = {};
   std::vector<Stamp> pending;
   std::vector<Event> free_events;
   // set once every piece of it exists (pipe_init)

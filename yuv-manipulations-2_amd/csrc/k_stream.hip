@@ -6,6 +6,8 @@
 //     (DCTYUV::dump / DCTYUVPlane::dumpTo, DCT.cpp:63-73, 160-173, and the
 //     serial compaction of applyDCTPlane, :314-322): a scan of per-tile
 //     totals, then the chunks of each tile;
+//   * k_gather_sizes + k_gather_heads + k_stream_gather: crop and join, a
+//     byte gather of chunks from stream to stream (at the end of the file);
 //
 // Stream layout: u32 plane_size[3]; per plane p:
 //   u32 nblocks, u32 content_size, u8 chunk_size[nblocks], u8 content[...].
@@ -18,6 +20,7 @@
 #include "codec_common.hpp"
 #include "k_chain.hpp"
 #include "k_stream.hpp"
+#include "stream_gather.h"
 
 namespace myyuv_gpu {
 
@@ -502,6 +505,218 @@ __global__ __launch_bounds__(256) void k_stream_out(const uint32_t* __restrict__
       *reinterpret_cast<uint32_t*>(out + P + k) = w;
     } else {  // the plane's last chunk (the next plane's header follows), or the end of `cap`
       for (uint32_t i = 0; i < rem; i++) out[P + k + i] = (uint8_t)(w >> (8 * i));
+    }
+  }
+}
+
+// ---- crop and join (include/myyuv_hip.h; the run map: stream_gather.h) ------
+//
+// Both are byte gathers: nothing is Huffman-decoded.  After k_scan_chain over
+// the source streams (header checks, offsets at 64-block group starts):
+//   k_gather_sizes: every output block's size byte, in destination order, into
+//     a workspace table (zeros for a source whose header is bad);
+//   k_scan_chain (encode-side mode) over that table: the destination offsets;
+//   k_gather_heads: one wave per output frame: plane headers, plane sizes, the
+//     stream's size and the capacity check, as k_tile_scan writes them;
+//   k_stream_gather: one wave per run (stream_gather.h), grid (runs, frames):
+//     the run's size bytes and its content bytes, one contiguous range on
+//     both sides;
+//   k_gather_check (host-buffer calls, rarely): the plane-content check alone.
+// Source frame of output frame f, stream t of the map: f * cols * rows + t.
+using myyuv_gather::GatherMap;
+
+__global__ __launch_bounds__(256) void k_gather_sizes(const uint8_t* __restrict__ in, uint32_t cap_in,
+                                                      const StreamDesc* __restrict__ desc, GatherMap M,
+                                                      uint8_t* __restrict__ gsz) {
+  const uint32_t f = blockIdx.y, gd = blockIdx.x * 256 + threadIdx.x;
+  if (gd >= M.dcum[3]) return;
+  const int p = plane_of(M.dcum, gd);
+  auto sel3 = [p](uint32_t a0, uint32_t a1, uint32_t a2) { return p == 0 ? a0 : (p == 1 ? a1 : a2); };
+  const uint32_t tbw = sel3(M.tbw[0], M.tbw[1], M.tbw[2]), tbh = sel3(M.tbh[0], M.tbh[1], M.tbh[2]);
+  const uint32_t jd = gd - sel3(0u, M.dcum[1], M.dcum[2]);
+  const uint32_t dbw = tbw * M.cols;
+  const uint32_t row = jd / dbw, col = jd - row * dbw;
+  const uint32_t tx = col / tbw, lx = col - tx * tbw;
+  const uint32_t ty = row / tbh, ly = row - ty * tbh;
+  const uint32_t js = (sel3(M.by[0], M.by[1], M.by[2]) + ly) * sel3(M.sbw[0], M.sbw[1], M.sbw[2]) +
+                      sel3(M.bx[0], M.bx[1], M.bx[2]) + lx;
+  const uint32_t sf = f * (M.cols * M.rows) + ty * M.cols + tx;
+  const StreamDesc* d = desc + sf;
+  uint32_t s = 0;
+  if (!d->bad) s = in[(size_t)sf * cap_in + sel3(d->sizes_pos[0], d->sizes_pos[1], d->sizes_pos[2]) + js];
+  gsz[(size_t)f * M.dcum[3] + gd] = (uint8_t)s;
+}
+
+__global__ __launch_bounds__(64) void k_gather_heads(const uint32_t* __restrict__ dloff,
+                                                     const uint32_t* __restrict__ dtpre, GatherMap M,
+                                                     uint8_t* __restrict__ out, uint32_t cap,
+                                                     uint32_t report_cap, uint32_t* __restrict__ out_size,
+                                                     unsigned long long* __restrict__ err) {
+  // report_cap = 0 (the host-buffer calls): `cap` is the library's own bound,
+  // 36 + size bytes + every source byte, which only a stream whose size table
+  // overruns its declared content can exceed; k_stream_gather reports that
+  // (MYYUV_E_PLANE_CONTENT), and the caller's capacity is checked on the host
+  const uint32_t f = blockIdx.x, p = threadIdx.x;
+  if (p >= 3) return;
+  const uint32_t dnblk = M.dcum[3], dnt = (dnblk + kScanTile - 1) / kScanTile;
+  dloff += (size_t)f * dnblk;
+  dtpre += (size_t)f * (dnt + 1);
+  const uint32_t c0 = p == 0 ? 0u : (p == 1 ? M.dcum[1] : M.dcum[2]);
+  const uint32_t c1 = p == 0 ? M.dcum[1] : (p == 1 ? M.dcum[2] : M.dcum[3]);
+  const uint32_t total = dtpre[dnt];
+  const uint32_t ppre = scanned(dloff, dtpre, c0);
+  const uint32_t pend = p < 2 ? scanned(dloff, dtpre, c1) : total;
+  const uint64_t bytes = 12ull + 24ull + dnblk + total;
+  if (p == 0) {
+    out_size[f] = (uint32_t)bytes;
+    if (bytes > cap && report_cap) record_error(err, 0, 5 /* MYYUV_E_CAPACITY, any frame */);
+  }
+  if (bytes > cap) return;  // (nothing of the frame is written: k_stream_gather returns too)
+  uint8_t* o = out + (size_t)f * cap;
+  const uint32_t nb = c1 - c0, content = pend - ppre;
+  const uint64_t hpos = 12ull + 8ull * p + c0 + ppre;
+  const uint32_t vals[2] = {nb, content};
+  for (int k = 0; k < 8; k++) o[hpos + k] = (uint8_t)(vals[k >> 2] >> (8 * (k & 3)));
+  const uint32_t psize = 8 + nb + content;
+  for (int k = 0; k < 4; k++) o[4 * p + k] = (uint8_t)(psize >> (8 * k));
+}
+
+// The plane-content check of the runs alone (k_stream_gather's, the source
+// side of its offsets; grid (runs, frames), one wave per run): reads size
+// bytes, writes nothing but the error word, and does not depend on any
+// capacity.  The host-buffer calls launch it when a result exceeds their own
+// bound (36 + size bytes + every source byte), which only a stream whose size
+// table overruns its declared content can do: k_stream_gather has then written
+// nothing and checked nothing.
+__global__ __launch_bounds__(64) void k_gather_check(const uint8_t* __restrict__ in, uint32_t cap_in,
+                                                     const StreamDesc* __restrict__ desc,
+                                                     const uint32_t* __restrict__ loff,
+                                                     const uint32_t* __restrict__ tpre, GatherMap M, uint32_t fbase,
+                                                     unsigned long long* __restrict__ err) {
+  const uint32_t lane = threadIdx.x, f = blockIdx.y;
+  const myyuv_gather::Run R = myyuv_gather::run_at(M, blockIdx.x);  // (wave-uniform)
+  const int p = (int)R.plane;
+  auto sel3 = [p](uint32_t a0, uint32_t a1, uint32_t a2) { return p == 0 ? a0 : (p == 1 ? a1 : a2); };
+  const uint32_t sf = f * (M.cols * M.rows) + R.stream;
+  const uint32_t snblk = M.scum[3], snt = (snblk + kScanTile - 1) / kScanTile;
+  in += (size_t)sf * cap_in;
+  loff += (size_t)sf * snblk;
+  tpre += (size_t)sf * (snt + 1);
+  const uint32_t scum_p = sel3(0u, M.scum[1], M.scum[2]);
+  const uint32_t js = R.src, jg = js & ~63u, npre = js - jg;
+  const StreamDesc dsc = desc[sf];
+  if (dsc.bad) return;  // (k_scan_chain recorded it)
+  const uint32_t pre_g = scanned(loff, tpre, scum_p + jg) - scanned(loff, tpre, scum_p);
+  const uint32_t spos = sel3(dsc.sizes_pos[0], dsc.sizes_pos[1], dsc.sizes_pos[2]);
+  const uint32_t csize = sel3(dsc.content_size[0], dsc.content_size[1], dsc.content_size[2]);
+  const bool live = lane < R.n;
+  const uint32_t s0 = in[spos + js + (live ? lane : R.n - 1u)];
+  const uint32_t sp = in[spos + jg + (lane < npre ? lane : 0u)];
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_dpp(live ? s0 : 0u), 63);
+  const uint32_t spre = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_dpp(lane < npre ? sp : 0u), 63);
+  if ((uint64_t)pre_g + spre + total > csize && lane == 0)
+    record_error(err, 2ull * (((uint64_t)fbase + sf) * snblk + scum_p), 9 /* MYYUV_E_PLANE_CONTENT */);
+}
+
+// One run: up to 64 chunks, 0 .. 64 * 255 bytes, from source byte A to
+// destination byte D of two 4-byte-aligned buffers; A - D is anything mod 4.
+// The copy is laid out on the DESTINATION's dwords: the bytes before the
+// first dword boundary inside the run and after the last one (at most 3 each;
+// those dwords belong in part to the neighbouring runs, other waves' work, or
+// to the size table or the next plane's header) are byte loads and byte
+// stores.  Every dword in between is the run's alone: lane l takes 16
+// destination bytes per round (a dwordx4 store), which are source bytes a ..
+// a + 15 with a & 3 = q, the same q for the whole run: a dwordx4 load of the
+// aligned words under them plus, when q != 0, the next word, funnel-shifted
+// by q bytes (v_alignbyte_b32).  The run's last, partial quad goes dword by
+// dword.  Every source word loaded holds at least one byte of the run, so no
+// load leaves the stream rounded to its dwords.
+__global__ __launch_bounds__(64) void k_stream_gather(const uint8_t* __restrict__ in, uint32_t cap_in,
+                                                      const StreamDesc* __restrict__ desc,
+                                                      const uint32_t* __restrict__ loff,
+                                                      const uint32_t* __restrict__ tpre,
+                                                      const uint8_t* __restrict__ gsz,
+                                                      const uint32_t* __restrict__ dloff,
+                                                      const uint32_t* __restrict__ dtpre, GatherMap M,
+                                                      uint32_t fbase, uint8_t* __restrict__ out, uint32_t cap_out,
+                                                      unsigned long long* __restrict__ err) {
+  const uint32_t lane = threadIdx.x, f = blockIdx.y;
+  const myyuv_gather::Run R = myyuv_gather::run_at(M, blockIdx.x);  // (wave-uniform)
+  const int p = (int)R.plane;
+  auto sel3 = [p](uint32_t a0, uint32_t a1, uint32_t a2) { return p == 0 ? a0 : (p == 1 ? a1 : a2); };
+  const uint32_t sf = f * (M.cols * M.rows) + R.stream;
+  const uint32_t snblk = M.scum[3], dnblk = M.dcum[3];
+  const uint32_t snt = (snblk + kScanTile - 1) / kScanTile, dnt = (dnblk + kScanTile - 1) / kScanTile;
+  in += (size_t)sf * cap_in;
+  loff += (size_t)sf * snblk;
+  tpre += (size_t)sf * (snt + 1);
+  gsz += (size_t)f * dnblk;
+  dloff += (size_t)f * dnblk;
+  dtpre += (size_t)f * (dnt + 1);
+  out += (size_t)f * cap_out;
+  const uint32_t scum_p = sel3(0u, M.scum[1], M.scum[2]);
+  const uint32_t dcum_p = sel3(0u, M.dcum[1], M.dcum[2]), dcum_p1 = sel3(M.dcum[1], M.dcum[2], M.dcum[3]);
+  // the run's first block on both sides, its 64-block group's first, and the
+  // group's blocks in front of the run (k_decode_region's scheme, twice)
+  const uint32_t js = R.src, jg = js & ~63u, npre = js - jg;
+  const uint32_t jd = R.dst, jdg = jd & ~63u, npd = jd - jdg;
+  const StreamDesc dsc = desc[sf];
+  const uint32_t lo_p = loff[scum_p], tp_p = tpre[scum_p / kScanTile];
+  const uint32_t lo_g = loff[scum_p + jg], tp_g = tpre[(scum_p + jg) / kScanTile];
+  const uint32_t dlo_p = dloff[dcum_p], dtp_p = dtpre[dcum_p / kScanTile];
+  const uint32_t dlo_g = dloff[dcum_p + jdg], dtp_g = dtpre[(dcum_p + jdg) / kScanTile];
+  const uint32_t dtotal = dtpre[dnt];
+  const uint32_t dp = gsz[dcum_p + jdg + (lane < npd ? lane : 0u)];
+  if (dsc.bad || (12ull + 24ull + dnblk + dtotal) > cap_out) return;  // (k_scan_chain / k_gather_heads recorded it)
+  const bool live = lane < R.n;
+  const uint32_t spos = sel3(dsc.sizes_pos[0], dsc.sizes_pos[1], dsc.sizes_pos[2]);
+  const uint32_t cpos = sel3(dsc.content_pos[0], dsc.content_pos[1], dsc.content_pos[2]);
+  const uint32_t csize = sel3(dsc.content_size[0], dsc.content_size[1], dsc.content_size[2]);
+  // (the header checks placed the size table and the content below min(size word, cap_in))
+  const uint32_t s0 = in[spos + js + (live ? lane : R.n - 1u)];
+  const uint32_t sp = in[spos + jg + (lane < npre ? lane : 0u)];
+  const uint32_t s = live ? s0 : 0u;
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_dpp(s), 63);
+  const uint32_t spre = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_dpp(lane < npre ? sp : 0u), 63);
+  const uint32_t dpre = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_dpp(lane < npd ? dp : 0u), 63);
+  const uint32_t pre0 = (lo_g + tp_g) - (lo_p + tp_p) + spre;  // the run's first byte inside the plane's content
+  uint32_t T = total;
+  if ((uint64_t)pre0 + total > csize) {  // a chunk of the run ends beyond the declared content
+    if (lane == 0)
+      record_error(err, 2ull * (((uint64_t)fbase + sf) * snblk + scum_p), 9 /* MYYUV_E_PLANE_CONTENT */);
+    T = csize > pre0 ? csize - pre0 : 0u;
+  }
+  // (the capacity guard once more, directly in front of the first store:
+  // nothing of a frame larger than cap_out is written)
+  if ((12ull + 24ull + dnblk + dtotal) > cap_out) return;
+  // the size bytes (DCTYUVPlane layout: after the plane's 8-byte header)
+  const uint64_t zpos = 12ull + 8ull * (p + 1) + (dlo_p + dtp_p) + dcum_p + jd;
+  if (live) out[zpos + lane] = (uint8_t)s;
+  const uint64_t D = 12ull + 8ull * (p + 1) + dcum_p1 + (dlo_g + dtp_g) + dpre;
+  const uint32_t A = cpos + pre0;
+  const uint32_t lead = min((4u - (uint32_t)(D & 3u)) & 3u, T);
+  const uint32_t ndw = (T - lead) >> 2, tail = (T - lead) & 3u;
+  if (lane < lead) out[D + lane] = in[A + lane];
+  if (lane >= 4u && lane - 4u < tail) out[D + T - tail + (lane - 4u)] = in[A + T - tail + (lane - 4u)];
+  const uint32_t a0 = A + lead, q = a0 & 3u;
+  const uint32_t* sw = reinterpret_cast<const uint32_t*>(in) + (a0 >> 2);
+  uint8_t* d0 = out + D + lead;  // (4-byte aligned)
+  for (uint32_t u = lane; 4u * u < ndw; u += 64u) {
+    const uint32_t nd = min(4u, ndw - 4u * u);
+    const uint32_t* s4 = sw + 4u * u;
+    if (nd == 4u) {
+      const Dw4 v = *reinterpret_cast<const Dw4*>(s4);
+      const uint32_t x = q ? s4[4] : 0u;
+      *reinterpret_cast<Dw4*>(d0 + 16u * u) =
+          Dw4{__builtin_amdgcn_alignbyte(v.y, v.x, q), __builtin_amdgcn_alignbyte(v.z, v.y, q),
+              __builtin_amdgcn_alignbyte(v.w, v.z, q), __builtin_amdgcn_alignbyte(x, v.w, q)};
+    } else {
+      uint32_t w[4];
+#pragma unroll
+      for (uint32_t j = 0; j < 4; j++) w[j] = j < nd + (q ? 1u : 0u) ? s4[j] : 0u;
+#pragma unroll
+      for (uint32_t j = 0; j < 3; j++)
+        if (j < nd) *reinterpret_cast<uint32_t*>(d0 + 16u * u + 4u * j) = __builtin_amdgcn_alignbyte(w[j + 1], w[j], q);
     }
   }
 }

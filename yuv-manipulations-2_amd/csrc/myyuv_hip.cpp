@@ -8,6 +8,7 @@
 //   scaled:     parse -> scan -> decode_scaled (every block, at 1/2, 1/4 or 1/8 size)
 //   requantise: parse -> scan -> requant (decode + rescale) -> K2 (+ overflow pass) -> K4
 //   transform:  parse -> scan -> coef_xform (decode + move + rescale) -> K2 (+ overflow pass) -> K4
+//   crop, join: parse -> scan -> gather_sizes -> scan -> gather_heads -> stream_gather (bytes only)
 // Every launch goes to one stream; nothing synchronises inside the
 // device-resident entry points, so frames pipeline back to back.
 // The context, the owners of its HIP resources and the entry points'
@@ -1423,6 +1424,252 @@ int myyuv_gpu_dct_transform_device(myyuv_hip_handle c, const void* d_payload, co
                        d_out_sizes, stream);
 }
 
+// ---- crop and join (defined in myyuv_hip.h) ---------------------------------
+namespace {
+
+using myyuv_gather::GatherMap;
+
+// Workspace of a gather launch: the scan of the source streams (Gs: the source
+// geometry, its batch the launch's source streams) and, for `nout` output
+// frames of dblk blocks, the size-byte table (1 B per block) and the
+// destination scan (4 B per block plus tile words).  Nothing of the 471 B per
+// block the codec calls reserve.
+int reserve_gather(myyuv_hip_ctx* c, const FrameGeom& Gs, uint32_t dblk, uint32_t nout) {
+  if (int e = reserve_scan(c, Gs)) return e;
+  const uint32_t dnt = ceil_div(dblk, kScanTile);
+  int e = 0;
+  e |= c->gsz.grow((size_t)nout * dblk);
+  e |= c->gloff.grow((size_t)nout * dblk * 4);
+  e |= c->gtiles.grow((size_t)nout * (dnt + 1) * 4);
+  const size_t st_bytes = (size_t)nout * (dnt + 1) * 8;
+  if (c->status.n < st_bytes) {  // (as reserve_scan: zeroed before any kernel reads it)
+    e |= c->status.grow(st_bytes);
+    if (!e && (hipMemset(c->status.p, 0, st_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+      e |= MYYUV_E_HIP;
+  }
+  return e ? MYYUV_E_HIP : 0;
+}
+
+// One launch: output frame f (Gd.nframes of them, at d_out + f * cap_out, its
+// size at d_size_out[f]) from the source streams f * nsub .. f * nsub + nsub - 1
+// (nsub = M.cols * M.rows; stream k at d_in + k * cap_in, its size at
+// d_size_in[k]).  Gs: the source geometry with the launch's nsub * nframes
+// streams as its batch and fbase the first one's index in the caller's batch
+// (of source streams: the error keys count in them).  report_cap: a frame
+// larger than cap_out is MYYUV_E_CAPACITY in the error word (the device
+// forms); the host-buffer forms pass their own bound and judge the size read
+// back themselves (gather_host_finish).
+int launch_gather(myyuv_hip_ctx* c, const FrameGeom& Gs, const FrameGeom& Gd, const GatherMap& M, const void* d_in,
+                  const uint32_t* d_size_in, uint32_t cap_in, void* d_out, uint32_t cap_out, uint32_t* d_size_out,
+                  bool report_cap, hipStream_t s) {
+  const uint32_t nsrc = Gs.nframes, nout = Gd.nframes;
+  const uint32_t snt = ceil_div(Gs.cum[3], kScanTile), dnt = ceil_div(Gd.cum[3], kScanTile);
+  unsigned long long* err = c->err.as<unsigned long long>();
+  StreamDesc* desc = c->desc.as<StreamDesc>();
+  const uint8_t* in = static_cast<const uint8_t*>(d_in);
+  uint8_t* out = static_cast<uint8_t*>(d_out);
+  int e = 0;
+  ScanSrc SS, SD;
+  for (int i = 0; i < 4; i++) SS.cum[i] = Gs.cum[i], SD.cum[i] = Gd.cum[i];
+  for (int p = 0; p < 3; p++) SS.pos[p] = 0, SD.pos[p] = Gd.cum[p];  // (the table holds the planes back to back)
+  e |= launch(c, MYYUV_K_SCAN, k_scan_chain, dim3(snt, nsrc), dim3(256), s, in, cap_in, SS, d_size_in, cap_in, Gs, desc,
+              c->loff.as<uint32_t>(), c->tiles.as<uint32_t>(), snt, c->status.as<unsigned long long>(), next_epoch(c),
+              err);
+  e |= launch(c, MYYUV_K_SCAN, k_gather_sizes, dim3(ceil_div(Gd.cum[3], 256), nout), dim3(256), s, in, cap_in,
+              (const StreamDesc*)desc, M, c->gsz.as<uint8_t>());
+  e |= launch(c, MYYUV_K_SCAN, k_scan_chain, dim3(dnt, nout), dim3(256), s, c->gsz.as<const uint8_t>(), Gd.cum[3], SD,
+              (const uint32_t*)nullptr, 0u, Gd, (StreamDesc*)nullptr, c->gloff.as<uint32_t>(),
+              c->gtiles.as<uint32_t>(), dnt, c->status.as<unsigned long long>(), next_epoch(c), err);
+  e |= launch(c, MYYUV_K_SCAN, k_gather_heads, dim3(nout), dim3(kWave), s, c->gloff.as<const uint32_t>(),
+              c->gtiles.as<const uint32_t>(), M, out, cap_out, report_cap ? 1u : 0u, d_size_out, err);
+  e |= launch(c, MYYUV_K_GATHER, k_stream_gather, dim3(M.rcum[3], nout), dim3(kWave), s, in, cap_in,
+              (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(),
+              c->gsz.as<const uint8_t>(), c->gloff.as<const uint32_t>(), c->gtiles.as<const uint32_t>(), M,
+              Gs.fbase, out, cap_out, err);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+// The join's grid: tiles of whole 16 x 16 units, at least one each way, no
+// 32-bit wrap, an output frame the compressor accepts (Gd: its geometry) and
+// at most 65,535 tiles (the scan's grid takes one row per tile).
+int make_join(uint32_t cols, uint32_t rows, uint32_t tw, uint32_t th, FrameGeom& Gd) {
+  if (cols == 0 || rows == 0 || tw == 0 || th == 0 || ((tw | th) & 15u)) return MYYUV_E_ARG;
+  if ((uint64_t)cols * tw > 0xFFFFFFFFull || (uint64_t)rows * th > 0xFFFFFFFFull) return MYYUV_E_ARG;
+  if ((uint64_t)cols * rows > 65535ull) return MYYUV_E_ARG;
+  if (make_geom(cols * tw, rows * th, Gd)) return MYYUV_E_ARG;
+  return 0;
+}
+
+// Upper bound of a gather's result: its headers and size bytes, and no more
+// content than the sources hold.
+uint32_t gather_bound(uint32_t dblk, uint64_t src_bytes) {
+  const uint64_t b = 36ull + dblk + src_bytes;
+  return b > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)((b + 3) & ~3ull);
+}
+
+// The host-buffer calls' device part and their epilogue: the streams are in
+// c->rqsrc (stream k at k * cap_in), their sizes at psz[0 .. nsub), the
+// result goes to c->payload and its size to psz[nsub].
+int gather_host_finish(myyuv_hip_ctx* c, const FrameGeom& Gs, const FrameGeom& Gd, const GatherMap& M,
+                       uint32_t cap_in, uint32_t bound, uint8_t* out, uint32_t cap, uint32_t* out_size,
+                       int64_t* bad_block, hipStream_t s) {
+  const uint32_t nsub = M.cols * M.rows;
+  uint32_t* psz = c->psize.as<uint32_t>();
+  int e = launch_gather(c, Gs, Gd, M, c->rqsrc.p, psz, cap_in, c->payload.p, bound, psz + nsub, false, s);
+  if (e) return e;
+  uint32_t nout = 0;
+  if (hipMemcpyAsync(&nout, psz + nsub, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return MYYUV_E_HIP;
+  e = read_err(c, s, bad_block);  // (synchronises)
+  if (!e && nout > bound) {
+    // `bound` holds every byte of the sources, so only a size table that
+    // overruns its plane's declared content selects more: k_stream_gather
+    // wrote and checked nothing, and the check runs on its own
+    // (MYYUV_E_PLANE_CONTENT comes before the caller's capacity)
+    if (launch(c, MYYUV_K_SCAN, k_gather_check, dim3(M.rcum[3], Gd.nframes), dim3(kWave), s,
+               static_cast<const uint8_t*>(c->rqsrc.p), cap_in, c->desc.as<const StreamDesc>(),
+               c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), M, Gs.fbase,
+               c->err.as<unsigned long long>()))
+      return MYYUV_E_HIP;
+    if (!(e = read_err(c, s, bad_block))) e = MYYUV_E_HIP;  // (cannot be: see above)
+  }
+  if (e) {
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  *out_size = nout;
+  if (nout > cap) return MYYUV_E_CAPACITY;
+  if (d2h(out, c->payload.p, nout, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+}  // namespace
+
+int myyuv_gpu_dct_crop(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h, uint32_t rx,
+                       uint32_t ry, uint32_t rw, uint32_t rh, uint8_t* out, uint32_t cap, uint32_t* out_size,
+                       int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payload || !out || !out_size) return MYYUV_E_ARG;
+  FrameGeom G, R;
+  RegionSegs S;
+  int e;
+  if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G)) ||
+      (e = make_region(w, h, rx, ry, rw, rh, R, S)))
+    return e;
+  if (ranges_overlap(payload, size, out, cap)) return MYYUV_E_ARG;
+  const GatherMap M = myyuv_gather::crop_map(w, h, rx, ry, rw, rh);
+  Entry en(c);
+  hipStream_t s = en.s;
+  const uint32_t cap_in = (size + 3) & ~3u;
+  const uint32_t bound = gather_bound(R.cum[3], size);
+  if ((e = reserve_gather(c, G, R.cum[3], 1))) return e;
+  if (c->rqsrc.grow(cap_in) || c->payload.grow(bound) || c->psize.grow(8)) return MYYUV_E_HIP;
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (hipMemsetAsync(static_cast<uint8_t*>(c->rqsrc.p) + (cap_in - 4), 0, 4, s) != hipSuccess ||
+      h2d(c->rqsrc.p, payload, size, s) ||
+      hipMemcpyAsync(c->psize.p, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  return gather_host_finish(c, G, R, M, cap_in, bound, out, cap, out_size, bad_block, s);
+}
+
+int myyuv_gpu_dct_crop_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_payload_sizes,
+                              uint32_t cap_in, uint32_t nframes, uint32_t w, uint32_t h, uint32_t rx, uint32_t ry,
+                              uint32_t rw, uint32_t rh, void* d_out, uint32_t cap_out, uint32_t* d_out_sizes,
+                              void* stream) {
+  if (!c || !d_payload || !d_payload_sizes || !d_out || !d_out_sizes) return MYYUV_E_ARG;
+  FrameGeom G, R;
+  RegionSegs S;
+  int e;
+  if ((e = make_geom(w, h, G)) || (e = set_batch(G, nframes)) || (e = make_region(w, h, rx, ry, rw, rh, R, S)))
+    return e;
+  if (((uintptr_t)d_payload & 3) || ((uintptr_t)d_out & 3) || (nframes > 1 && ((cap_in | cap_out) & 3)))
+    return MYYUV_E_ARG;
+  if (ranges_overlap(d_payload, (uint64_t)cap_in * nframes, d_out, (uint64_t)cap_out * nframes)) return MYYUV_E_ARG;
+  const GatherMap M = myyuv_gather::crop_map(w, h, rx, ry, rw, rh);
+  Entry en(c, stream);
+  // (as several launches past the kernels' 32-bit block numbers or the grid's 65,535 frames)
+  const uint32_t per = std::min(launch_frames(G, c->launch_blocks), 65535u);
+  FrameGeom GL = G, RL = R;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve_gather(c, GL, R.cum[3], GL.nframes))) return e;
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GL.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0))) || (e = set_batch(RL, GL.nframes))) return e;
+    const uint8_t* src = static_cast<const uint8_t*>(d_payload) + (size_t)f0 * cap_in;
+    uint8_t* dst = static_cast<uint8_t*>(d_out) + (size_t)f0 * cap_out;
+    if ((e = launch_gather(c, GL, RL, M, src, d_payload_sizes + f0, cap_in, dst, cap_out, d_out_sizes + f0, true,
+                           en.s)))
+      return e;
+  }
+  return 0;
+}
+
+int myyuv_gpu_dct_join(myyuv_hip_handle c, const uint8_t* const* payloads, const uint32_t* sizes, uint32_t cols,
+                       uint32_t rows, uint32_t tw, uint32_t th, uint8_t* out, uint32_t cap, uint32_t* out_size,
+                       int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payloads || !sizes || !out || !out_size) return MYYUV_E_ARG;
+  // (the grid's counts first: they say how many streams there are to look at)
+  if (cols == 0 || rows == 0 || (uint64_t)cols * rows > 65535ull) return MYYUV_E_ARG;
+  const uint32_t nsub = cols * rows;
+  FrameGeom G, Gd;
+  int e = 0;
+  uint64_t src_bytes = 0;
+  uint32_t cap_in = 4;
+  for (uint32_t t = 0; t < nsub; t++)
+    if (!payloads[t]) return MYYUV_E_ARG;
+  for (uint32_t t = 0; t < nsub; t++) {
+    if ((e = host_parse_headers(payloads[t], sizes[t]))) {
+      // tile t's first block, as the device batches report it (-1 for tile 0)
+      const uint64_t tblk = (uint64_t)(tw / 8) * (th / 8) + 2ull * (tw / 16) * (th / 16);
+      if (bad_block && t) *bad_block = (int64_t)(t * tblk);
+      return e;
+    }
+    src_bytes += sizes[t];
+    cap_in = std::max(cap_in, (sizes[t] + 3) & ~3u);
+  }
+  if ((e = make_geom(tw, th, G)) || (e = make_join(cols, rows, tw, th, Gd)) || (e = set_batch(G, nsub))) return e;
+  for (uint32_t t = 0; t < nsub; t++)
+    if (ranges_overlap(payloads[t], sizes[t], out, cap)) return MYYUV_E_ARG;
+  const GatherMap M = myyuv_gather::join_map(cols, rows, tw, th);
+  Entry en(c);
+  hipStream_t s = en.s;
+  const uint32_t bound = gather_bound(Gd.cum[3], src_bytes);
+  if ((e = reserve_gather(c, G, Gd.cum[3], 1))) return e;
+  if (c->rqsrc.grow((size_t)cap_in * nsub) || c->payload.grow(bound) || c->psize.grow((size_t)(nsub + 1) * 4))
+    return MYYUV_E_HIP;
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  // (every slot's bytes past its stream are defined: the copy's loads are whole dwords)
+  if (hipMemsetAsync(c->rqsrc.p, 0, (size_t)cap_in * nsub, s) != hipSuccess) return MYYUV_E_HIP;
+  for (uint32_t t = 0; t < nsub; t++)
+    if (h2d(static_cast<uint8_t*>(c->rqsrc.p) + (size_t)t * cap_in, payloads[t], sizes[t], s)) return MYYUV_E_HIP;
+  if (hipMemcpyAsync(c->psize.p, sizes, (size_t)nsub * 4, hipMemcpyHostToDevice, s) != hipSuccess) return MYYUV_E_HIP;
+  return gather_host_finish(c, G, Gd, M, cap_in, bound, out, cap, out_size, bad_block, s);
+}
+
+int myyuv_gpu_dct_join_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_payload_sizes,
+                              uint32_t cap_in, uint32_t cols, uint32_t rows, uint32_t tw, uint32_t th, void* d_out,
+                              uint32_t cap_out, uint32_t* d_out_size, void* stream) {
+  if (!c || !d_payload || !d_payload_sizes || !d_out || !d_out_size) return MYYUV_E_ARG;
+  FrameGeom G, Gd;
+  int e;
+  if ((e = make_geom(tw, th, G)) || (e = make_join(cols, rows, tw, th, Gd))) return e;
+  const uint32_t nsub = cols * rows;
+  if ((e = set_batch(G, nsub))) return e;
+  if (((uintptr_t)d_payload & 3) || ((uintptr_t)d_out & 3) || (nsub > 1 && (cap_in & 3))) return MYYUV_E_ARG;
+  if (ranges_overlap(d_payload, (uint64_t)cap_in * nsub, d_out, cap_out)) return MYYUV_E_ARG;
+  const GatherMap M = myyuv_gather::join_map(cols, rows, tw, th);
+  Entry en(c, stream);
+  if ((e = reserve_gather(c, G, Gd.cum[3], 1))) return e;
+  return launch_gather(c, G, Gd, M, d_payload, d_payload_sizes, cap_in, d_out, cap_out, d_out_size, true, en.s);
+}
+
 // ---- host-buffer batches, pipelined ------------------
 //
 // The batch is cut into chunks of B frames, alternating between two device
@@ -1715,7 +1962,7 @@ int myyuv_gpu_dct_decompress_to_bmp_frames(myyuv_hip_handle c, const uint8_t* co
 }
 
 int myyuv_hip_profile(myyuv_hip_handle c, int enable) {
-  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_COUNT) - 1u : 0u);
+  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_TOTAL) - 1u : 0u);
 }
 
 int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
@@ -1724,25 +1971,30 @@ int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
   DeviceGuard g(c->device);
   (void)hipStreamSynchronize(c->stream);
   drain_profile(c);
-  c->prof = mask & ((1u << MYYUV_K_COUNT) - 1u);
-  for (int k = 0; k < MYYUV_K_COUNT; k++) {
+  c->prof = mask & ((1u << MYYUV_K_TOTAL) - 1u);
+  for (int k = 0; k < MYYUV_K_TOTAL; k++) {
     c->ms[k] = 0;
     c->launches[k] = 0;
   }
   return 0;
 }
 
-int myyuv_hip_kernel_stats(myyuv_hip_handle c, double ms[MYYUV_K_COUNT],
-                           int64_t launches[MYYUV_K_COUNT]) {
+int myyuv_hip_kernel_stats_n(myyuv_hip_handle c, uint32_t n, double* ms, int64_t* launches) {
   if (!c || !ms || !launches) return MYYUV_E_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
   drain_profile(c);
-  for (int k = 0; k < MYYUV_K_COUNT; k++) {
-    ms[k] = c->ms[k];
-    launches[k] = c->launches[k];
+  for (uint32_t k = 0; k < n; k++) {
+    ms[k] = k < MYYUV_K_TOTAL ? c->ms[k] : 0.0;
+    launches[k] = k < MYYUV_K_TOTAL ? c->launches[k] : 0;
   }
   return 0;
+}
+
+// (the first MYYUV_K_COUNT ids: the length its callers' arrays have)
+int myyuv_hip_kernel_stats(myyuv_hip_handle c, double ms[MYYUV_K_COUNT],
+                           int64_t launches[MYYUV_K_COUNT]) {
+  return myyuv_hip_kernel_stats_n(c, MYYUV_K_COUNT, ms, launches);
 }
 
 }  // extern "C"

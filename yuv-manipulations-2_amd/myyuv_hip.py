@@ -27,6 +27,12 @@ KERNELS = ["fdct_quant", "huff_encode", "scan_tiles", "stream_out", "encode_tile
 (K_FDCT, K_HUFF_ENC, K_SCAN, K_COMPACT, K_ENCODE_TILE, K_HUFF_DEC, K_IDCT, K_HUFF_WIDE,
  K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP, K_REGION, K_SCALED, K_REQUANT,
  K_COEF_XF) = range(len(KERNELS))
+# KERNELS is the fixed-length list of myyuv_hip_kernel_stats (MYYUV_K_COUNT: part of that call's
+# ABI, it does not grow); ids from there on are read with myyuv_hip_kernel_stats_n, and
+# Codec.profile / Codec.kernel_stats take and return the names of KERNELS_ALL
+KERNELS_ALL = KERNELS + ["stream_gather"]
+K_GATHER = KERNELS_ALL.index("stream_gather")
+K_TOTAL = len(KERNELS_ALL)  # MYYUV_K_TOTAL
 # MYYUV_XF_*: bit 0 mirror x, bit 1 mirror y, bit 2 swap (transpose first, then the mirrors)
 (XF_NONE, XF_FLIP_H, XF_FLIP_V, XF_ROT180, XF_TRANSPOSE, XF_ROT90, XF_ROT270, XF_TRANSVERSE) = range(8)
 XF_NAMES = {"none": 0, "flip_h": 1, "flip_v": 2, "rot180": 3, "transpose": 4, "rot90": 5, "rot270": 6,
@@ -42,7 +48,8 @@ EXPORTS = [
     "myyuv_hip_create", "myyuv_hip_destroy", "myyuv_hip_strerror", "myyuv_dct_payload_bound",
     "myyuv_gpu_dct_compress", "myyuv_gpu_dct_decompress", "myyuv_hip_reserve",
     "myyuv_gpu_dct_compress_device", "myyuv_gpu_dct_decompress_device", "myyuv_hip_sync_status",
-    "myyuv_hip_profile", "myyuv_hip_profile_kernels", "myyuv_hip_kernel_stats", "myyuv_gpu_fdct_blocks",
+    "myyuv_hip_profile", "myyuv_hip_profile_kernels", "myyuv_hip_kernel_stats", "myyuv_hip_kernel_stats_n",
+    "myyuv_gpu_fdct_blocks",
     "myyuv_gpu_huff_encode_blocks", "myyuv_hip_reserve_batch", "myyuv_gpu_dct_compress_batch_device",
     "myyuv_gpu_dct_decompress_batch_device", "myyuv_gpu_bmp_to_iyuv", "myyuv_gpu_bmp_to_iyuv_device",
     "myyuv_gpu_dct_compress_batch", "myyuv_gpu_dct_compress_frames", "myyuv_gpu_dct_decompress_frames",
@@ -54,6 +61,7 @@ EXPORTS = [
     "myyuv_gpu_dct_decompress_scaled_to_bmp",
     "myyuv_gpu_dct_requantize", "myyuv_gpu_dct_requantize_device",
     "myyuv_gpu_dct_transform", "myyuv_gpu_dct_transform_device",
+    "myyuv_gpu_dct_crop", "myyuv_gpu_dct_crop_device", "myyuv_gpu_dct_join", "myyuv_gpu_dct_join_device",
 ]
 
 _lib = None
@@ -117,6 +125,8 @@ def load():
     L.myyuv_hip_profile_kernels.argtypes = [vp, ctypes.c_uint32]
     L.myyuv_hip_kernel_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_int64)]
+    L.myyuv_hip_kernel_stats_n.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_int64)]
     L.myyuv_gpu_fdct_blocks.argtypes = [vp, u8p, u32, ctypes.POINTER(ctypes.c_float),
                                         ctypes.POINTER(ctypes.c_int16)]
     L.myyuv_gpu_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u8p, u8p]
@@ -150,6 +160,11 @@ def load():
     L.myyuv_gpu_dct_transform.argtypes = [vp, u8p, u32, u32, u32, u8p, u32, u8p, u8p, u32, ctypes.POINTER(u32),
                                           i64p]
     L.myyuv_gpu_dct_transform_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, u32, u8p, vp, u32, vp, vp]
+    L.myyuv_gpu_dct_crop.argtypes = [vp, u8p, u32, u32, u32, u32, u32, u32, u32, u8p, u32, ctypes.POINTER(u32), i64p]
+    L.myyuv_gpu_dct_crop_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, u32, u32, u32, vp, u32, vp, vp]
+    L.myyuv_gpu_dct_join.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u32), u32, u32, u32, u32, u8p, u32,
+                                     ctypes.POINTER(u32), i64p]
+    L.myyuv_gpu_dct_join_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, vp, u32, vp, vp]
     L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -598,6 +613,77 @@ class Codec:
         if rc:
             raise CodecError(rc)
 
+    # -- crop and join: a rectangle cut out of a DCT stream, a grid of streams laid
+    # side by side as one, on the chunk bytes (defined in include/myyuv_hip.h) --
+    def crop(self, payload, w, h, region):
+        """DCTYUV payload of a w x h frame -> the payload of its rectangle
+        region = (rx, ry, rw, rh) (multiples of 16), as bytes."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        out = np.empty(36 + src.nbytes, np.uint8)  # (a part of the source never exceeds it)
+        n = self.crop_into(src, w, h, region, out)
+        return out[:n].tobytes()
+
+    def crop_into(self, payload, w, h, region, out):
+        """crop from / into the caller's C-contiguous uint8 arrays, which must
+        not overlap; returns the result's size.  A short `out` fails with
+        E_CAPACITY (CodecError.need holds the size needed)."""
+        src = _u8_array(payload, "payload")
+        dst = _u8_array(out, "out", writable=True)
+        rx, ry, rw, rh = region
+        size = ctypes.c_uint32(0)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_crop(self._h, _u8(src), src.nbytes, w, h, rx, ry, rw, rh, _u8(dst), dst.nbytes,
+                                       ctypes.byref(size), ctypes.byref(bad))
+        if rc:
+            err = CodecError(rc, bad.value)
+            err.need = size.value
+            raise err
+        return size.value
+
+    def crop_device(self, d_payload, d_sizes, cap_in, nframes, w, h, region, d_out, cap_out, d_out_sizes,
+                    stream=None):
+        """Device-resident batch, one rectangle for all frames (requantize_device's
+        layout and rules); asynchronous, errors through sync_status."""
+        rx, ry, rw, rh = region
+        rc = load().myyuv_gpu_dct_crop_device(self._h, d_payload, d_sizes, cap_in, nframes, w, h, rx, ry, rw, rh,
+                                              d_out, cap_out, d_out_sizes, stream)
+        if rc:
+            raise CodecError(rc)
+
+    def join(self, payloads, cols, rows, tw, th):
+        """cols * rows DCTYUV payloads of tw x th frames, row-major -> the payload
+        of the (cols*tw) x (rows*th) frame, as bytes."""
+        out = np.empty(max(1, 36 + sum(len(p) for p in payloads)), np.uint8)
+        n = self.join_into(payloads, cols, rows, tw, th, out)
+        return out[:n].tobytes()
+
+    def join_into(self, payloads, cols, rows, tw, th, out):
+        """join into the caller's C-contiguous uint8 array; returns the result's
+        size (crop_into's rules).  len(payloads) must be cols * rows."""
+        if len(payloads) != cols * rows:
+            raise ValueError("join: cols * rows payloads are required")
+        srcs = [np.ascontiguousarray(np.frombuffer(memoryview(p).cast("B"), np.uint8)) for p in payloads]
+        dst = _u8_array(out, "out", writable=True)
+        ptrs = (ctypes.c_void_p * max(1, len(srcs)))(*[s.ctypes.data for s in srcs])
+        sizes = (ctypes.c_uint32 * max(1, len(srcs)))(*[s.nbytes for s in srcs])
+        size = ctypes.c_uint32(0)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_join(self._h, ptrs, sizes, cols, rows, tw, th, _u8(dst), dst.nbytes,
+                                       ctypes.byref(size), ctypes.byref(bad))
+        if rc:
+            err = CodecError(rc, bad.value)
+            err.need = size.value
+            raise err
+        return size.value
+
+    def join_device(self, d_payload, d_sizes, cap_in, cols, rows, tw, th, d_out, cap_out, d_out_size, stream=None):
+        """Device-resident join: tile t at d_payload + t*cap_in (size d_sizes[t])
+        -> the stream at d_out, its size at *d_out_size (device u32)."""
+        rc = load().myyuv_gpu_dct_join_device(self._h, d_payload, d_sizes, cap_in, cols, rows, tw, th, d_out, cap_out,
+                                              d_out_size, stream)
+        if rc:
+            raise CodecError(rc)
+
     # -- device-resident API (pointers are device addresses, e.g. torch data_ptr) --
     def reserve(self, w, h):
         rc = load().myyuv_hip_reserve(self._h, w, h)
@@ -645,18 +731,19 @@ class Codec:
         if kernels is None:
             rc = load().myyuv_hip_profile(self._h, 1 if enable else 0)
         else:
-            mask = sum(1 << KERNELS.index(k) for k in kernels) if enable else 0
+            mask = sum(1 << KERNELS_ALL.index(k) for k in kernels) if enable else 0
             rc = load().myyuv_hip_profile_kernels(self._h, mask)
         if rc:
             raise CodecError(rc)
 
     def kernel_stats(self):
-        ms = (ctypes.c_double * len(KERNELS))()
-        n = (ctypes.c_int64 * len(KERNELS))()
-        rc = load().myyuv_hip_kernel_stats(self._h, ms, n)
+        """{name: (summed ms, launches)} for every name of KERNELS_ALL."""
+        ms = (ctypes.c_double * K_TOTAL)()
+        n = (ctypes.c_int64 * K_TOTAL)()
+        rc = load().myyuv_hip_kernel_stats_n(self._h, K_TOTAL, ms, n)
         if rc:
             raise CodecError(rc)
-        return {KERNELS[i]: (ms[i], n[i]) for i in range(len(KERNELS))}
+        return {KERNELS_ALL[i]: (ms[i], n[i]) for i in range(K_TOTAL)}
 
     def tinfo_guard(self, ntiles, arm):
         """Diagnostic (not in include/myyuv_hip.h): arm=True writes a canary
