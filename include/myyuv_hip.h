@@ -620,6 +620,91 @@ int myyuv_gpu_dct_join_device(myyuv_hip_handle h, const void* d_payload, const u
                               uint32_t cap_in, uint32_t cols, uint32_t rows, uint32_t tile_w, uint32_t tile_h,
                               void* d_out, uint32_t cap_out, uint32_t* d_out_size, void* stream);
 
+/* Compare: how far a frame is from another — PSNR's squared error and a block
+ * SSIM — between two raw IYUV frames, or between a DCT stream and a raw frame
+ * without the stream's decoded frame ever existing in HBM: the fused decoder
+ * loads the reference frame's rows where the full decode stores its own and
+ * keeps integer sums.  No reference program emits these figures, so the
+ * definition is stated here, bit for bit.  Every figure the device produces is
+ * an integer; there is no floating point in the kernels.
+ *
+ * Per plane the block grid is the codec's own: 8x8 blocks, row-major,
+ * k = (y/8) * bw + x/8.  With x the 64 reference samples and y the 64 test
+ * samples (u8) of block k:
+ *   sse_k  = sum (x - y)^2                                 (<= 64 * 255^2 = 4,161,600)
+ *   max_k  = max |x - y|
+ *   Sx = sum x, Sy = sum y, Sxx = sum x^2, Syy = sum y^2, Sxy = sum x y      (u32)
+ *   C1 = 26634 (= round(4096 (0.01 * 255)^2)),  C2 = 239708 (= round(4096 (0.03 * 255)^2))
+ *   A1 = 2 Sx Sy + C1              A2 = 2 (64 Sxy - Sx Sy) + C2       (A2 may be negative)
+ *   B1 = Sx^2 + Sy^2 + C1          B2 = 64 (Sxx + Syy) - Sx^2 - Sy^2 + C2
+ *   ssim_k = floor(A1 A2 2^24 / (B1 B2))        floor towards minus infinity; int32 in [-2^24, 2^24]
+ * This is SSIM over non-overlapping 8x8 windows, the means and variances kept
+ * as exact integers scaled by 64 and 4096.  B1 < 2^29 and B2 < 2^27, so
+ * B1 B2 < 2^56; |A1 A2| <= B1 B2 always (2ab <= a^2 + b^2 in both factors);
+ * identical blocks give exactly 2^24.  Everything is symmetric in x and y.
+ * The arithmetic is yuv-manipulations-2_amd/csrc/metric.h, shared by the
+ * kernels and the host check.
+ *
+ * A plane's record sums its blocks: sse, ssim_sum = sum ssim_k, nblocks, and
+ * max_abs = max max_k.  The optional map holds every block's pair, in the
+ * codec's block order (planes Y, U, V; frame f's block g at f * blocks_per_frame
+ * + g).  The integers are the contract; the two functions below turn them
+ * into the usual numbers on the host. */
+typedef struct { uint64_t sse; int64_t ssim_sum; uint32_t nblocks; uint32_t max_abs; } myyuv_plane_metric;
+typedef struct { myyuv_plane_metric plane[3]; } myyuv_frame_metric;      /* Y, U, V */
+typedef struct { uint32_t sse; int32_t ssim; } myyuv_block_metric;
+/* 10 log10(255^2 nsamples / sse), +inf at sse == 0. */
+double myyuv_metric_psnr(uint64_t sse, uint64_t nsamples);
+/* ssim_sum / (nblocks 2^24). */
+double myyuv_metric_ssim(int64_t ssim_sum, uint64_t nblocks);
+/* Two raw frames (W*H*3/2 bytes each), host buffers.  map_or_null: one entry
+ * per block of the frame.  Checks: the handle and pointers (MYYUV_E_ARG), then
+ * the % 8 dimension checks of myyuv_gpu_dct_decompress.  On any error *out is
+ * left zeroed. */
+int myyuv_gpu_iyuv_compare(myyuv_hip_handle h, const uint8_t* ref, const uint8_t* test, uint32_t width,
+                           uint32_t height, myyuv_frame_metric* out, myyuv_block_metric* map_or_null);
+/* Device-resident batch: test frame f at d_test + f*W*H*3/2 against reference
+ * frame f at d_ref + f*W*H*3/2 (ref_frames == nframes) or against the one
+ * frame at d_ref (ref_frames == 1) -> d_out[f], and d_map[f * blocks_per_frame
+ * + g] when d_map is not null; asynchronous on `stream` (NULL = the
+ * context's).  d_ref, d_test, d_out and d_map are 8-byte aligned.  Every
+ * record of d_out is written whole by every call (the kernels keep per-group
+ * totals in the workspace, 16 B per 64 blocks, and a small kernel adds them
+ * up: there is no accumulator to clear).  Argument errors (a null pointer,
+ * ref_frames not in {1, nframes}, nframes == 0, alignment: MYYUV_E_ARG; the
+ * dimensions) are returned at once, before any device is touched. */
+int myyuv_gpu_iyuv_compare_device(myyuv_hip_handle h, const void* d_ref, const void* d_test, uint32_t nframes,
+                                  uint32_t ref_frames, uint32_t width, uint32_t height,
+                                  myyuv_frame_metric* d_out, myyuv_block_metric* d_map_or_null, void* stream);
+/* A DCT stream (test) against a raw frame (reference), host buffers.  Checks
+ * and errors: those of myyuv_gpu_dct_decompress, in its order (ref_iyuv and
+ * out among the pointers).  The whole chunk of every block is decoded, so a
+ * malformed stream gives exactly myyuv_gpu_dct_decompress's code and
+ * *bad_block.  On any error *out is left zeroed (the map is unspecified).
+ * Workspace: the scaled decode's (132 B per block: the scan and the
+ * coefficient buffer for irregular tables), plus 16 B per 64 blocks of
+ * per-group totals, the records and the map.  The
+ * host-buffer form copies the stream and the reference frame to the device and
+ * 72 B (and the map) back. */
+int myyuv_gpu_dct_compare(myyuv_hip_handle h, const uint8_t* payload, uint32_t size, uint32_t width,
+                          uint32_t height, const uint8_t quality[3], const uint8_t* ref_iyuv,
+                          myyuv_frame_metric* out, myyuv_block_metric* map_or_null, int64_t* bad_block);
+/* Device-resident batch: stream f at d_payload + f*cap (cap a multiple of 4
+ * when nframes > 1, its size at d_payload_sizes[f]) against reference frame f
+ * (ref_frames == nframes) or frame 0 (ref_frames == 1) of d_ref -> d_out[f] and
+ * the map as above; d_payload 4-byte, d_ref, d_out and d_map 8-byte aligned;
+ * asynchronous on `stream` (NULL = the context's).  Every record of d_out is
+ * written whole by every call.  Argument errors are returned at once (a null
+ * handle or pointer, ref_frames not in {1, nframes}: MYYUV_E_ARG, before any
+ * device is touched), device-side errors through myyuv_hip_sync_status
+ * (batch-global block index f * blocks_per_frame + block); the records of a
+ * batch that reported one are unspecified.  Both decoder arrangements
+ * (MYYUV_DECODER) run the same fused kernel. */
+int myyuv_gpu_dct_compare_device(myyuv_hip_handle h, const void* d_payload, const uint32_t* d_payload_sizes,
+                                 uint32_t cap, uint32_t nframes, uint32_t width, uint32_t height,
+                                 const uint8_t quality[3], const void* d_ref, uint32_t ref_frames,
+                                 myyuv_frame_metric* d_out, myyuv_block_metric* d_map_or_null, void* stream);
+
 /* Host-buffer batches (many frames per call; §7 step 9:
  * transfers overlapped with the kernels).  The batch runs in chunks of up to
  * 8 frames through two device slots: chunk k's host -> device copies, chunk
@@ -698,6 +783,13 @@ int myyuv_hip_sync_status(myyuv_hip_handle h, void* stream, int64_t* bad_block);
 #define MYYUV_K_COUNT 17
 #define MYYUV_K_GATHER 17    /* byte gather of crop and join, wave per run (stream_gather) */
 #define MYYUV_K_TOTAL 18     /* every id above is below this */
+/* MYYUV_K_TOTAL is frozen as MYYUV_K_COUNT is (callers size their arrays for
+ * myyuv_hip_kernel_stats_n with it).  Later ids follow it; MYYUV_K_END is the
+ * bound of all ids, and the length to pass for all of them. */
+#define MYYUV_K_COMPARE 18   /* fused decoder against a reference frame (decode_compare) */
+#define MYYUV_K_FRAME_CMP 19 /* two raw frames against each other (frame_compare) */
+#define MYYUV_K_METRIC_SUM 20 /* the compare kernels' per-group totals summed per plane (metric_reduce) */
+#define MYYUV_K_END 21       /* every id is below this */
 int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 /* As myyuv_hip_profile, but stamps only the kernels whose bit (1 << MYYUV_K_*)
  * is set in `mask` (0 disables): event stamping costs host and queue time per
@@ -705,8 +797,8 @@ int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 int myyuv_hip_profile_kernels(myyuv_hip_handle h, uint32_t mask);
 int myyuv_hip_kernel_stats(myyuv_hip_handle h, double ms[MYYUV_K_COUNT],
                            int64_t launches[MYYUV_K_COUNT]);
-/* The same for the first min(n, MYYUV_K_TOTAL) ids; entries from
- * MYYUV_K_TOTAL on, if any, are set to 0. */
+/* The same for the first min(n, MYYUV_K_END) ids; entries from
+ * MYYUV_K_END on, if any, are set to 0. */
 int myyuv_hip_kernel_stats_n(myyuv_hip_handle h, uint32_t n, double* ms, int64_t* launches);
 
 /* Block-level entry points for known-answer tests (device round trip of one

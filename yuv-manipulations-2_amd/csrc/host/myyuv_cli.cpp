@@ -36,6 +36,10 @@
 // is this command, after -decompress or -to_bmp it is their option):
 //   myyuv_cli in.myyuv -crop X Y W H -o out.myyuv
 //   myyuv_cli -join COLS ROWS -o out.myyuv tile.myyuv...   (COLS * ROWS files, row-major)
+// how far two images of one size are from each other (compare,
+// include/myyuv_hip.h: PSNR and 8x8-block SSIM per plane, on the GPU; a
+// compressed side against a raw one is never decoded to memory):
+//   myyuv_cli a.myyuv -compare b.myyuv [-o report.txt]
 // and, beyond the reference CLI, many frames per invocation (SURVEY.md §8f
 // row 2; frames of one geometry share batched kernel launches):
 //   myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IN.myyuv...
@@ -44,6 +48,7 @@
 // each output is OUTDIR/<input file name>, byte-identical to the per-file
 // command's.
 #include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <functional>
@@ -83,6 +88,8 @@ void usage() {
             << "      (a compressed image's rectangle, still compressed: its chunks, untouched)\n"
             << "  myyuv_cli -join COLS ROWS -o OUT.myyuv TILE.myyuv...\n"
             << "      (COLS x ROWS compressed tiles of one size and quality, row-major, as one compressed image)\n"
+            << "  myyuv_cli IMAGE.myyuv -compare OTHER.myyuv [-o REPORT.txt]\n"
+            << "      (PSNR and 8x8-block SSIM per plane between two images of one size, compressed or not)\n"
             << "  myyuv_cli IMAGE.bmp -info\n"
             << "  myyuv_cli IMAGE.bmp -to_yuv IYUV -o OUT.myyuv\n"
             << "  myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IMAGE.myyuv...\n"
@@ -154,6 +161,55 @@ myyuv::YUV compress_dct(const myyuv::YUV& yuv, const std::vector<std::string>& p
   uint8_t q[3];
   dct_qualities(params, q);
   return yuv.compress(myyuv::YUV::Compressions::DCT, q, 3);
+}
+
+constexpr const char* kCompareHelp =
+    "Invalid argument, -compare must be followed by an image and at most `-o /path/to/report.txt`\n";
+
+// The report of `IMAGE -compare OTHER` (IMAGE is the reference side; the
+// figures are symmetric): a line per plane, one for all samples, and the
+// block with the lowest SSIM (ties: the first in plane, then block order).
+std::string compare_report(const myyuv::YUV& a, const myyuv::YUV& b) {
+  std::vector<myyuv_block_metric> map;
+  const myyuv_frame_metric m = a.compare(b, &map);
+  const uint32_t w = a.getWidth(), h = a.getHeight();
+  const uint64_t samples[3] = {(uint64_t)w * h, (uint64_t)w * h / 4, (uint64_t)w * h / 4};
+  char line[256];
+  auto psnr_text = [](uint64_t sse, uint64_t n) {
+    char t[64];
+    if (sse == 0)
+      std::snprintf(t, sizeof t, "inf");
+    else
+      std::snprintf(t, sizeof t, "%.6f", myyuv_metric_psnr(sse, n));
+    return std::string(t);
+  };
+  std::string text;
+  uint64_t sse = 0, nb = 0;
+  int64_t ss = 0;
+  for (int p = 0; p < 3; p++) {
+    const myyuv_plane_metric& r = m.plane[p];
+    std::snprintf(line, sizeof line, "%c: psnr %s dB ssim %.6f sse %llu max %u\n", "YUV"[p],
+                  psnr_text(r.sse, samples[p]).c_str(), myyuv_metric_ssim(r.ssim_sum, r.nblocks),
+                  (unsigned long long)r.sse, r.max_abs);
+    text += line;
+    sse += r.sse;
+    ss += r.ssim_sum;
+    nb += r.nblocks;
+  }
+  std::snprintf(line, sizeof line, "all: psnr %s dB ssim %.6f\n", psnr_text(sse, (uint64_t)w * h * 3 / 2).c_str(),
+                myyuv_metric_ssim(ss, nb));
+  text += line;
+  size_t k = 0;
+  for (size_t i = 1; i < map.size(); i++)
+    if (map[i].ssim < map[k].ssim) k = i;
+  const size_t ny = (size_t)(w / 8) * (h / 8), nc = (size_t)(w / 16) * (h / 16);
+  const int p = k < ny ? 0 : (k < ny + nc ? 1 : 2);
+  const size_t local = k - (p == 0 ? 0 : (p == 1 ? ny : ny + nc));
+  const size_t bw = p == 0 ? w / 8 : w / 16;
+  std::snprintf(line, sizeof line, "worst block: plane %c x %zu y %zu sse %u ssim %.6f\n", "YUV"[p], (local % bw) * 8,
+                (local / bw) * 8, map[k].sse, (double)map[k].ssim / 16777216.0);
+  text += line;
+  return text;
 }
 
 int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& args_in) {
@@ -300,6 +356,33 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     const float ms = elapsed_ms([&] { out = myyuvDCT::crop_DCT_planar(yuv, r[0], r[1], r[2], r[3]); });
     std::cout << "YUV DCT crop (" << r[0] << " " << r[1] << " " << r[2] << " " << r[3] << ") : " << ms << " ms\n";
     out.dump(args[a + 1]);
+    return 0;
+  }
+  if (cmd == "-compare") {  // B.myyuv [-o REPORT.txt]: how far this image is from B
+    if (args.size() != a + 2 && !(args.size() == a + 4 && args[a + 2] == "-o")) {
+      std::cout << kCompareHelp;
+      usage();
+      return 1;
+    }
+    std::string text;
+    try {
+      const myyuv::YUV other(args[a + 1]);
+      if (other.getWidth() != yuv.getWidth() || other.getHeight() != yuv.getHeight() ||
+          other.getFourccFormat() != yuv.getFourccFormat()) {
+        std::cout << "Nothing to compare, the images differ in size or format\n";
+        return 1;
+      }
+      text = compare_report(yuv, other);
+    } catch (const std::exception& e) {  // an unreadable B, a stream that does not decode
+      std::cout << "Error comparing: " << e.what() << '\n';
+      return 1;
+    }
+    std::cout << text;
+    if (args.size() == a + 4) {
+      std::ofstream f(args[a + 3], std::ios::binary);
+      f << text;
+      if (!f) throw std::runtime_error("Error opening file to write " + args[a + 3]);
+    }
     return 0;
   }
   if (cmd == "-decompress") {

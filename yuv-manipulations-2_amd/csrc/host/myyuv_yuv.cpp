@@ -418,6 +418,54 @@ YUV crop_region(const YUV& yuv, uint32_t rx, uint32_t ry, uint32_t rw, uint32_t 
   return res;
 }
 
+// Compare (include/myyuv_hip.h).  Either side raw or DCT-compressed: two raw
+// frames through myyuv_gpu_iyuv_compare; a stream and a raw frame through the
+// fused myyuv_gpu_dct_compare, the stream's decoded frame never written; of
+// two streams `other` is decoded first and *this takes the fused path.  The
+// metric is symmetric, so which side is the reference does not matter.
+myyuv_frame_metric YUV::compare(const YUV& other, std::vector<myyuv_block_metric>* map) const {
+  auto side_ok = [](const YUV& y) {
+    if (!y.isValidHeader() || !y.data) throw std::runtime_error("YUV is invalid");
+    if (y.getFourccFormat() != FourccFormats::IYUV) throw std::runtime_error("Incorrect format");
+    if (y.getCompression() == Compressions::NONE) {
+      if (y.header.data_size < (uint64_t)y.header.width * y.header.height * 3 / 2)
+        throw std::runtime_error("YUV is invalid");
+    } else if (y.getCompression() != Compressions::DCT) {
+      throw std::runtime_error("Error this decompression is unimplemented");
+    } else if (y.header.compression_params_size != 3 || !y.compression_params) {
+      throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
+    }
+  };
+  side_ok(*this);
+  side_ok(other);
+  if (header.width != other.header.width || header.height != other.header.height ||
+      getFourccFormat() != other.getFourccFormat())
+    throw std::runtime_error("Error comparing: the frames differ in size or format");
+  const uint32_t w = header.width, h = header.height;
+  const uint64_t nblk = (uint64_t)(w / 8) * (h / 8) + 2ull * (w / 16) * (h / 16);
+  if (map) map->assign(nblk ? nblk : 1, myyuv_block_metric{0, 0});
+  myyuv_block_metric* mp = map ? map->data() : nullptr;
+  myyuv_frame_metric out;
+  std::memset(&out, 0, sizeof(out));
+  int64_t bad = -1;
+  int rc;
+  if (!isCompressed() && !other.isCompressed()) {
+    rc = myyuv_gpu_iyuv_compare(t_codec.get(), data, other.data, w, h, &out, mp);
+  } else if (isCompressed() && other.isCompressed()) {
+    const YUV raw = other.decompress();
+    rc = myyuv_gpu_dct_compare(t_codec.get(), data, header.data_size, w, h, compression_params, raw.data, &out, mp,
+                               &bad);
+  } else {
+    const YUV& s = isCompressed() ? *this : other;
+    const YUV& r = isCompressed() ? other : *this;
+    rc = myyuv_gpu_dct_compare(t_codec.get(), s.data, s.header.data_size, w, h, s.compression_params, r.data, &out,
+                               mp, &bad);
+  }
+  if (rc) fail(rc);
+  if (map) map->resize(nblk);
+  return out;
+}
+
 }  // namespace myyuv
 
 namespace myyuvDCT {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "myyuv_bmp.hpp"
+#include "myyuv_hip.h"
 
 namespace myyuv {
 
@@ -95,6 +96,13 @@ class YUV {
   YUV compress(Compression compression, const void* params, uint32_t params_size) const;
   YUV decompress() const;
   bool isCompressed() const noexcept { return getCompression() != Compressions::NONE; }
+  // PSNR's and block SSIM's integers against `other` (include/myyuv_hip.h,
+  // Compare): the three plane records, and with `map` every block's pair in
+  // the codec's block order.  Either side may be raw or DCT-compressed; a
+  // compressed side is never decoded to memory when the other is raw.  Frames
+  // of different size or format: std::runtime_error("Error comparing: the
+  // frames differ in size or format").
+  myyuv_frame_metric compare(const YUV& other, std::vector<myyuv_block_metric>* map = nullptr) const;
   void load(const std::string& path);
   void load(const BMP& bmp, FourccFormat format);
   void dump(const std::string& path) const;

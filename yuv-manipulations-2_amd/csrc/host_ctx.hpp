@@ -73,6 +73,12 @@ __global__ void k_gather_check(const uint8_t*, uint32_t, const StreamDesc*, cons
 __global__ void k_stream_gather(const uint8_t*, uint32_t, const StreamDesc*, const uint32_t*, const uint32_t*,
                                 const uint8_t*, const uint32_t*, const uint32_t*, myyuv_gather::GatherMap, uint32_t,
                                 uint8_t*, uint32_t, unsigned long long*);
+__global__ void k_decode_compare(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
+                                 const uint32_t*, FrameGeom, uint32_t, uint32_t, const QTables*, uint4*, const uint8_t*,
+                                 uint32_t, uint4*, myyuv_block_metric*, unsigned long long*);
+__global__ void k_frame_compare(const uint8_t*, uint32_t, const uint8_t*, FrameGeom, uint32_t, uint32_t, uint4*,
+                                myyuv_block_metric*);
+__global__ void k_metric_reduce(const uint4*, uint32_t, uint32_t, uint32_t, myyuv_frame_metric*);
 template <int BPP>
 __global__ void k_bmp_to_iyuv(const uint8_t*, uint32_t, uint32_t, uint32_t, uint8_t*);
 template <int BPP, int LINEAR>
@@ -212,6 +218,11 @@ struct myyuv_hip_ctx {
   // destination scan's group offsets and tile prefixes (the source scan's are
   // loff / tiles; the status words serve both scans, one after the other)
   DevBuf gsz, gloff, gtiles;
+  // compare: the waves' totals (16 B per 64-block group) between the compare
+  // kernels and k_metric_reduce; for the host-buffer calls the plane records,
+  // the per-block map and the staged test frame (the reference frame is
+  // staged in `frame`)
+  DevBuf mpart, mrec, mmap, mtest;
   // profiling: the kernels' start/stop events until drain_profile reads
   // them; they are used again from launch to launch
   struct Stamp {
@@ -220,8 +231,8 @@ struct myyuv_hip_ctx {
   };
   uint32_t prof = 0;  // bit k: stamp kernel id k
   uint32_t skip = 0;  // diagnostic: bit k: do not launch kernel id k (myyuv_debug_skip_kernels)
-  double ms[MYYUV_K_TOTAL] = {};
-  int64_t launches[MYYUV_K_TOTAL] = {};
+  double ms[MYYUV_K_END] = {};
+  int64_t launches[MYYUV_K_END] = {};
   std::vector<Stamp> pending;
   std::vector<Event> free_events;
   // set once every piece of it exists (pipe_init)

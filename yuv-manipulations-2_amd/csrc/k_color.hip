@@ -1,5 +1,7 @@
 // k_color.hip — the colour conversions at the two ends of the pixel path:
-// K7 BMP -> IYUV (below) and K8 IYUV -> BMP (further down).
+// K7 BMP -> IYUV (below) and K8 IYUV -> BMP (further down); and, at the end,
+// the two pixel-side kernels of Compare: k_frame_compare (two raw frames) and
+// k_metric_reduce (the per-group totals of either compare kernel, per plane).
 //
 // K7: BMP (BGR / BGRA) -> IYUV 4:2:0, the step before compress
 // (SURVEY.md §8f row 3).  Replaces YUV(const BMP&, IYUV): bmp_to_yuv_map[IYUV]
@@ -28,6 +30,7 @@
 
 #include "codec_common.hpp"
 #include "color_div.hpp"
+#include "k_metric.hpp"
 
 namespace myyuv_gpu {
 
@@ -298,5 +301,97 @@ template __global__ void k_iyuv_to_bmp<3, 0>(const uint8_t*, uint32_t, uint32_t,
 template __global__ void k_iyuv_to_bmp<3, 1>(const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t*);
 template __global__ void k_iyuv_to_bmp<4, 0>(const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t*);
 template __global__ void k_iyuv_to_bmp<4, 1>(const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t*);
+
+// ---- compare --------------------------------------------------------------
+//
+// k_frame_compare: PSNR's and block SSIM's integers between two raw IYUV
+// frames in HBM (include/myyuv_hip.h, "Compare"; the arithmetic is metric.h).
+// The fused decoder's grid (k_decode_compare): one wave per 64-block group of
+// one plane (blockIdx.x: tiles_p0 groups of Y, tiles_p1 of U, then V) of frame
+// blockIdx.y, lane l the group's block l, so a wave's totals belong to one
+// plane.  A lane reads its block's 8 rows of both frames, 8 B each: the
+// group's blocks are consecutive in a block row, so a row of the wave is one
+// 512-B run.  Pure streaming: 128 B read per block, 8 B written with a map.
+// ref_fbytes: G.fbytes, or 0 when every frame is compared with one reference.
+__global__ __launch_bounds__(64) void k_frame_compare(const uint8_t* __restrict__ ref, uint32_t ref_fbytes,
+                                                      const uint8_t* __restrict__ test, FrameGeom G,
+                                                      uint32_t tiles_p0, uint32_t tiles_p1,
+                                                      uint4* __restrict__ part,
+                                                      myyuv_block_metric* __restrict__ map) {
+  const uint32_t lane = threadIdx.x, t = blockIdx.x, f = blockIdx.y;
+  const int p = t >= tiles_p0 ? (t >= tiles_p0 + tiles_p1 ? 2 : 1) : 0;
+  auto sel3 = [p](uint32_t a0, uint32_t a1, uint32_t a2) { return p == 0 ? a0 : (p == 1 ? a1 : a2); };
+  const uint32_t cum = sel3(G.cum[0], G.cum[1], G.cum[2]), nb = sel3(G.cum[1], G.cum[2], G.cum[3]) - cum;
+  const uint32_t poff = sel3(G.poff[0], G.poff[1], G.poff[2]);
+  const uint32_t pw = sel3(G.pw[0], G.pw[1], G.pw[2]), bw = sel3(G.bw[0], G.bw[1], G.bw[2]);
+  const uint64_t bmag = p == 0 ? G.bmag[0] : (p == 1 ? G.bmag[1] : G.bmag[2]);
+  const uint32_t local = (t - sel3(0u, tiles_p0, tiles_p0 + tiles_p1)) * kWave + lane;
+  const bool live = local < nb;
+  const uint32_t lc = live ? local : nb - 1;  // (lanes past the plane's end read its last block)
+  const uint32_t by = div_magic(lc, bmag), bx = lc - by * bw;
+  const uint32_t off = poff + by * 8u * pw + bx * 8u;
+  const uint8_t* x = ref + (size_t)f * ref_fbytes + off;
+  const uint8_t* y = test + (size_t)f * G.fbytes + off;
+  uint2 xr[8], yr[8];
+#pragma unroll
+  for (uint32_t r = 0; r < 8; r++) {
+    xr[r] = *reinterpret_cast<const uint2*>(x + r * pw);
+    yr[r] = *reinterpret_cast<const uint2*>(y + r * pw);
+  }
+  myyuv_metric::Sums s;
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    myyuv_metric::add_word(s, xr[r].x, yr[r].x);
+    myyuv_metric::add_word(s, xr[r].y, yr[r].y);
+  }
+  mt::finish(s, live, mt::wave_slot(part), map != nullptr ? map + (size_t)f * G.cum[3] + cum + lc : nullptr);
+}
+
+// k_metric_reduce: the waves' totals of either Compare kernel (one uint4 per
+// wave of the decoders' grid: sse, ssim, blocks, max; frame f's group t at
+// part[f * (t0 + t1 + t2) + t]) added up per plane.  One workgroup per plane
+// (blockIdx.x) of frame blockIdx.y; it writes the whole record, so nothing
+// needs clearing between calls.  Integer sums: their order cannot change them.
+__global__ __launch_bounds__(256) void k_metric_reduce(const uint4* __restrict__ part, uint32_t t0, uint32_t t1,
+                                                       uint32_t t2, myyuv_frame_metric* __restrict__ out) {
+  const uint32_t p = blockIdx.x, f = blockIdx.y;
+  const uint32_t first = p == 0 ? 0u : (p == 1 ? t0 : t0 + t1), cnt = p == 0 ? t0 : (p == 1 ? t1 : t2);
+  const uint4* src = part + (size_t)f * (t0 + t1 + t2) + first;
+  unsigned long long sse = 0;
+  long long ss = 0;
+  uint32_t n = 0, mx = 0;
+  for (uint32_t i = threadIdx.x; i < cnt; i += 256u) {
+    const uint4 v = src[i];
+    sse += v.x;
+    ss += (int32_t)v.y;
+    n += v.z;
+    mx = max(mx, v.w);
+  }
+  __shared__ unsigned long long s_sse[256];
+  __shared__ long long s_ss[256];
+  __shared__ uint32_t s_n[256], s_mx[256];
+  s_sse[threadIdx.x] = sse;
+  s_ss[threadIdx.x] = ss;
+  s_n[threadIdx.x] = n;
+  s_mx[threadIdx.x] = mx;
+  __syncthreads();
+  for (uint32_t k = 128; k > 0; k >>= 1) {
+    if (threadIdx.x < k) {
+      s_sse[threadIdx.x] += s_sse[threadIdx.x + k];
+      s_ss[threadIdx.x] += s_ss[threadIdx.x + k];
+      s_n[threadIdx.x] += s_n[threadIdx.x + k];
+      s_mx[threadIdx.x] = max(s_mx[threadIdx.x], s_mx[threadIdx.x + k]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    myyuv_plane_metric r;
+    r.sse = s_sse[0];
+    r.ssim_sum = s_ss[0];
+    r.nblocks = s_n[0];
+    r.max_abs = s_mx[0];
+    out[f].plane[p] = r;
+  }
+}
 
 }  // namespace myyuv_gpu

@@ -37,6 +37,7 @@
 #include "coef_xform.h"
 #include "huff_common.hpp"
 #include "idct_scaled.h"
+#include "k_metric.hpp"
 #include "k_stream.hpp"
 #include "requant.h"
 #include "xform_common.hpp"
@@ -1348,6 +1349,212 @@ __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_coef_xform(const uint8_t
   block_class_msz(R, msz, cls);
   rmask[g] = (uint8_t)m;
   binfo[g] = binfo_word(m, (uint32_t)msz, cls, nw[0] & 0xFFFFu);
+}
+
+// ---- compare --------------------------------------------------------------
+//
+// k_decode_compare: the fused decoder with a reference frame where
+// k_decode_idct has its output (include/myyuv_hip.h, "Compare").  Grid, decode,
+// DC-only shortcut and transform units are k_decode_idct's, decode_group
+// unchanged, so a malformed stream gives the full decode's code and block.
+// Where k_decode_idct stores a pixel row at block_row_offset(...), this kernel
+// has loaded the reference frame's row from the same offset (issued before the
+// unit's transform, which hides the latency) and adds the row's part of the
+// block's sums (metric.h).  A block's rows sit in 4 lanes of a 16-block unit,
+// in 8 lanes of an 8-block unit (mt::fold_lanes) and in one lane for a
+// DC-only block; one of them leaves the block's six sums in LDS at the block's
+// lane of the group (component-major, at the end of the value-position table,
+// dead after decode_group).  After the last unit lane l takes block l's sums and
+// the wave finishes as k_frame_compare does (mt::finish): the 24-step quotient
+// runs once per group, every lane busy, and the group's totals go to its slot
+// of `part` for k_metric_reduce (k_color.hip).  The decoded frame never exists
+// in HBM.  ref_fbytes: G.fbytes, or 0 when every frame is compared with one
+// reference frame.
+__global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_compare(const uint8_t* __restrict__ in,
+                                                      const uint32_t* __restrict__ in_size,
+                                                      uint32_t cap,
+                                                      const StreamDesc* __restrict__ desc,
+                                                      const uint32_t* __restrict__ local_off,
+                                                      const uint32_t* __restrict__ tile_pre,
+                                                      FrameGeom G, uint32_t tiles_p0,
+                                                      uint32_t tiles_p1, const QTables* __restrict__ qt,
+                                                      uint4* __restrict__ coef,
+                                                      const uint8_t* __restrict__ ref, uint32_t ref_fbytes,
+                                                      uint4* __restrict__ part,
+                                                      myyuv_block_metric* __restrict__ map,
+                                                      unsigned long long* __restrict__ err) {
+  static_assert(sizeof(uint4) * kStageQuads >= sizeof(float) * xf::kXfTile16, "the tile over the stage");
+  __shared__ uint4 stq[kStageQuads + 1 + kGposQuads];
+  __shared__ float sq[64];
+  __shared__ uint16_t s_blk[64];
+  const uint32_t lane = threadIdx.x;
+  if (lane == 0) stq[kStageQuads] = make_uint4(0u, 0u, 0u, 0u);  // (ordered by decode_group's barrier)
+  {
+    // the plane's Q table by LDS-DMA (landed by decode_group's final vmcnt wait)
+    const uint32_t t = blockIdx.x;
+    const int p = t >= tiles_p0 ? (t >= tiles_p0 + tiles_p1 ? 2 : 1) : 0;
+    __builtin_amdgcn_global_load_lds((const void*)&qt->q[p][lane], (__attribute__((address_space(3))) void*)sq, 4,
+                                     0, 0);
+  }
+  DecodeGroup D;
+  uint32_t nw[32];
+#pragma unroll
+  for (int w = 0; w < 32; w++) nw[w] = 0;
+  bool direct;
+  if (!decode_group(in, in_size, cap, desc, local_off, tile_pre, G, tiles_p0, tiles_p1, coef, err, stq, D, nw,
+                    direct)) {
+    // the frame's stream header is bad (k_scan_chain recorded it): the wave adds nothing
+    if (lane == 0) *mt::wave_slot(part) = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  if (D.live && direct) {  // decode_general wrote the block to coef (a table the reference never writes)
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      const uint4 v = coef[coef_quad(D.gbase + D.g, c)];
+      nw[4 * c] = v.x;
+      nw[4 * c + 1] = v.y;
+      nw[4 * c + 2] = v.z;
+      nw[4 * c + 3] = v.w;
+    }
+  }
+  const int p = D.p;
+  xf::Unit U;
+  U.p = p;
+  U.cum = G.cum[p];
+  U.nb = G.cum[p + 1] - G.cum[p];
+  U.poff = p == 0 ? G.poff[0] : (p == 1 ? G.poff[1] : G.poff[2]);
+  U.pw = p == 0 ? G.pw[0] : (p == 1 ? G.pw[1] : G.pw[2]);
+  U.bw = p == 0 ? G.bw[0] : (p == 1 ? G.bw[1] : G.bw[2]);
+  U.bmag = p == 0 ? G.bmag[0] : (p == 1 ? G.bmag[1] : G.bmag[2]);
+  U.local0 = 0;
+  const uint8_t* fr = ref + (size_t)D.f * ref_fbytes;
+  // LDS after the decode: the transpose tile over the stage (4608 B), then the
+  // unit's reference rows (xl: 4 words per lane, word m of lane l at
+  // xl[64 m + l], 1 KiB over the stage's end, the zero quad and the start of
+  // the value-position table), then the blocks' sums at the table's end
+  // (block l's component c at gs[64 c + l])
+  constexpr uint32_t kSumWords = 6 * 64, kRefWords = 4 * 64;
+  constexpr uint32_t kLdsWords = (kStageQuads + 1 + kGposQuads) * 4;
+  static_assert(xf::kXfTile16 + kRefWords + kSumWords <= kLdsWords, "tile, reference rows and sums");
+  uint32_t* xl = reinterpret_cast<uint32_t*>(stq) + xf::kXfTile16;
+  uint32_t* gs = reinterpret_cast<uint32_t*>(stq) + (kLdsWords - kSumWords);
+  auto put_sums = [gs](uint32_t l, const mt::Sums& s) {
+    gs[l] = s.sx;
+    gs[64 + l] = s.sy;
+    gs[128 + l] = s.sxx;
+    gs[192 + l] = s.syy;
+    gs[256 + l] = s.sxy;
+    gs[320 + l] = s.mx;
+  };
+  uint32_t acc = nw[0] & 0xFFFF0000u;
+#pragma unroll
+  for (int w = 1; w < 32; w++) acc |= nw[w];
+  const bool isdc = D.live && acc == 0u;
+  if (isdc) {  // the DC-only constant block (see k_decode_idct), against the block's 8 reference rows
+    uint2 rr[8];
+#pragma unroll
+    for (uint32_t r = 0; r < 8; r++)
+      rr[r] = *reinterpret_cast<const uint2*>(fr + xf::block_row_offset(U, D.g - U.cum, r));
+    constexpr float c0 = xf::c_dct[0];
+    const float z = (float)(int16_t)nw[0] * sq[0];  // dequantise (DCT.cpp:331)
+    const float u = 0.0f + c0 * z;                  // stage 1: the k = 0 term
+    float S = 0.0f + u * c0;                        // stage 2: the k = 0 term
+    S = __builtin_amdgcn_fmed3f(S, -128.0f, 127.0f);  // (as idct_rows, DCT.cpp:358-362)
+    uint32_t px = xf::bits(S + xf::kMagicPx);
+    if (__builtin_amdgcn_fractf(S) == 0.5f)
+      px = (uint32_t)((int)__builtin_truncf(S + __builtin_copysignf(xf::kHalfDown, S)) + 128);
+    const uint32_t v4 = (px & 0xFFu) * 0x01010101u;
+    mt::Sums s;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      myyuv_metric::add_word(s, rr[r].x, v4);
+      myyuv_metric::add_word(s, rr[r].y, v4);
+    }
+    put_sums(lane, s);
+  }
+  const uint64_t rest = __ballot(D.live && !isdc);
+  const uint32_t nrest = (uint32_t)__popcll(rest);
+  const uint32_t rrank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rest >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rest, 0u));
+  if (D.live && !isdc) s_blk[rrank] = (uint16_t)lane;  // compacted position -> the block's lane in the group
+  xf::wave_sync();  // (s_blk is read at the top of the first unit)
+  float* tile = reinterpret_cast<float*>(stq);
+#pragma unroll 1
+  for (uint32_t base = 0; base < nrest;) {
+    const bool wide = nrest - base > 8u;
+    const uint32_t span = wide ? 16u : 8u, stride = wide ? (uint32_t)xf::kTile : (uint32_t)xf::kTile8;
+    // the unit's reference rows, issued before its transform by LDS-DMA (they
+    // hold no register while it runs; the kernel sits at the register budget
+    // of its five waves per SIMD): lane (b, q) rows 2q, 2q + 1 of block b, or
+    // lane (b, r) row r.  Slots past the last block read the last block's.
+    const uint32_t ub = wide ? lane >> 2 : lane >> 3;
+    const uint32_t ur = wide ? 2u * (lane & 3u) : lane & 7u;
+    {
+      const uint32_t ul = s_blk[min(base + ub, nrest - 1u)];  // the block's lane in the group
+      const uint8_t* src = fr + xf::block_row_offset(U, D.g0 + ul - U.cum, ur);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the last unit's reads of xl)
+      __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)xl, 4, 0, 0);
+      __builtin_amdgcn_global_load_lds((const void*)(src + 4), (__attribute__((address_space(3))) void*)(xl + 64), 4,
+                                       0, 0);
+      if (wide) {
+        __builtin_amdgcn_global_load_lds((const void*)(src + U.pw),
+                                         (__attribute__((address_space(3))) void*)(xl + 128), 4, 0, 0);
+        __builtin_amdgcn_global_load_lds((const void*)(src + U.pw + 4),
+                                         (__attribute__((address_space(3))) void*)(xl + 192), 4, 0, 0);
+      }
+    }
+    const uint32_t s = rrank - base;
+    if (D.live && !isdc && rrank >= base && s < span) {
+      uint4* img = reinterpret_cast<uint4*>(tile + s * stride + (wide ? xf::img_word(s) : 0u));
+#pragma unroll
+      for (int c = 0; c < 8; c++) img[c] = make_uint4(nw[4 * c], nw[4 * c + 1], nw[4 * c + 2], nw[4 * c + 3]);
+    }
+    if (lane < span && base + lane >= nrest) {
+      uint4* img = reinterpret_cast<uint4*>(tile + lane * stride + (wide ? xf::img_word(lane) : 0u));
+#pragma unroll
+      for (int c = 0; c < 8; c++) img[c] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    xf::wave_sync();
+    mt::Sums ps;
+    if (wide) {
+      const uint32_t q = lane & 3u, b = lane >> 2;
+      uint2 w0, w1;
+      xf::idct_rows(tile + b * xf::kTile, q, b, sq, w0, w1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the reference rows are in xl
+      myyuv_metric::add_word(ps, xl[lane], w0.x);
+      myyuv_metric::add_word(ps, xl[64 + lane], w0.y);
+      myyuv_metric::add_word(ps, xl[128 + lane], w1.x);
+      myyuv_metric::add_word(ps, xl[192 + lane], w1.y);
+      mt::fold_lanes<4>(ps);
+      if (q == 0u && base + b < nrest) put_sums(s_blk[base + b], ps);
+    } else {
+      const uint32_t r = lane & 7u, b = lane >> 3;
+      float qc[8];  // the lane's column of the plane's Q table, Q[k][r]
+#pragma unroll
+      for (int k = 0; k < 8; k++) qc[k] = sq[8 * k + r];
+      const uint2 w = xf::idct_row8(tile + b * xf::kTile8, r, qc);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the reference rows are in xl
+      myyuv_metric::add_word(ps, xl[lane], w.x);
+      myyuv_metric::add_word(ps, xl[64 + lane], w.y);
+      mt::fold_lanes<8>(ps);
+      if (r == 0u && base + b < nrest) put_sums(s_blk[base + b], ps);
+    }
+    xf::wave_sync();  // the next unit rewrites the tile
+    base += span;
+  }
+  xf::wave_sync();  // the blocks' sums, from the lanes that left them to the blocks' own lanes
+  mt::Sums bs;
+  bs.sx = gs[lane];
+  bs.sy = gs[64 + lane];
+  bs.sxx = gs[128 + lane];
+  bs.syy = gs[192 + lane];
+  bs.sxy = gs[256 + lane];
+  bs.mx = gs[320 + lane];
+  // (the block's index built again from the lane: the 64-bit index of the
+  // coefficient buffer would otherwise stay live, one register pair too many,
+  // from the decode to here)
+  uint32_t gl = lane;
+  asm volatile("" : "+v"(gl));
+  mt::finish(bs, D.live, mt::wave_slot(part), map != nullptr ? map + (D.gbase + D.g0 + gl) : nullptr);
 }
 
 }  // namespace myyuv_gpu

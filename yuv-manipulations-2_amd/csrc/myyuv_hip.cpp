@@ -6,6 +6,8 @@
 //   decompress: parse -> scan -> K5 huff_decode -> K6 dequant_idct
 //   region:     parse -> scan -> decode_region (a rectangle's blocks only)
 //   scaled:     parse -> scan -> decode_scaled (every block, at 1/2, 1/4 or 1/8 size)
+//   compare:    parse -> scan -> decode_compare (every block, against a reference frame's rows);
+//               two raw frames: frame_compare
 //   requantise: parse -> scan -> requant (decode + rescale) -> K2 (+ overflow pass) -> K4
 //   transform:  parse -> scan -> coef_xform (decode + move + rescale) -> K2 (+ overflow pass) -> K4
 //   crop, join: parse -> scan -> gather_sizes -> scan -> gather_heads -> stream_gather (bytes only)
@@ -1306,6 +1308,212 @@ int myyuv_gpu_dct_decompress_scaled_to_bmp(myyuv_hip_handle c, const uint8_t* pa
   return 0;
 }
 
+// ---- compare (defined in myyuv_hip.h) ----------------------------------------
+namespace {
+
+void group_tiles(const FrameGeom& G, uint32_t& t0, uint32_t& t1, uint32_t& t2) {
+  t0 = ceil_div(G.cum[1] - G.cum[0], kWave);
+  t1 = ceil_div(G.cum[2] - G.cum[1], kWave);
+  t2 = ceil_div(G.cum[3] - G.cum[2], kWave);
+}
+
+// The waves' totals of a launch of G.nframes frames (16 B per 64-block group).
+int reserve_metric(myyuv_hip_ctx* c, const FrameGeom& G) {
+  uint32_t t0, t1, t2;
+  group_tiles(G, t0, t1, t2);
+  return c->mpart.grow((size_t)G.nframes * (t0 + t1 + t2) * sizeof(uint4)) ? MYYUV_E_HIP : 0;
+}
+
+// The records from the waves' totals.  Every wave of the compare kernels
+// writes its slot and k_metric_reduce writes every record whole: there is no
+// accumulator that a call could find stale, and nothing to clear.
+int launch_metric_reduce(myyuv_hip_ctx* c, const FrameGeom& G, myyuv_frame_metric* d_out, hipStream_t s) {
+  uint32_t t0, t1, t2;
+  group_tiles(G, t0, t1, t2);
+  return launch(c, MYYUV_K_METRIC_SUM, k_metric_reduce, dim3(3, G.nframes), dim3(256), s,
+                c->mpart.as<const uint4>(), t0, t1, t2, d_out);
+}
+
+// Two raw frames: test frame f at d_test + f * fbytes against reference frame
+// f (ref_fbytes = fbytes) or frame 0 (ref_fbytes = 0) of d_ref.
+int launch_frame_compare(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_ref, uint32_t ref_fbytes,
+                         const void* d_test, myyuv_frame_metric* d_out, myyuv_block_metric* d_map, hipStream_t s) {
+  const uint32_t nf = G.nframes;
+  uint32_t t0, t1, t2;
+  group_tiles(G, t0, t1, t2);
+  if (reserve_metric(c, G)) return MYYUV_E_HIP;
+  int e = launch(c, MYYUV_K_FRAME_CMP, k_frame_compare, dim3(t0 + t1 + t2, nf), dim3(kWave), s,
+              static_cast<const uint8_t*>(d_ref), ref_fbytes, static_cast<const uint8_t*>(d_test), G, t0, t1,
+              c->mpart.as<uint4>(), d_map);
+  e |= launch_metric_reduce(c, G, d_out, s);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+// A stream against a raw frame: the scan as launch_decompress runs it, then
+// k_decode_compare on k_decode_idct's grid, whatever MYYUV_DECODER says (the
+// split arrangement runs the same kernel).  Workspace: reserve_scaled.
+int launch_dct_compare(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_in, const uint32_t* d_size, uint32_t cap,
+                       const void* d_ref, uint32_t ref_fbytes, myyuv_frame_metric* d_out, myyuv_block_metric* d_map,
+                       hipStream_t s) {
+  const uint32_t nf = G.nframes;
+  const uint32_t ntiles = ceil_div(G.cum[3], kScanTile);
+  unsigned long long* err = c->err.as<unsigned long long>();
+  StreamDesc* desc = c->desc.as<StreamDesc>();
+  const uint8_t* in = static_cast<const uint8_t*>(d_in);
+  if (reserve_metric(c, G)) return MYYUV_E_HIP;
+  int e = 0;
+  ScanSrc SS;
+  for (int i = 0; i < 4; i++) SS.cum[i] = G.cum[i];
+  for (int p = 0; p < 3; p++) SS.pos[p] = 0;
+  e |= launch(c, MYYUV_K_SCAN, k_scan_chain, dim3(ntiles, nf), dim3(256), s, in, cap, SS, d_size, cap, G, desc,
+              c->loff.as<uint32_t>(), c->tiles.as<uint32_t>(), ntiles, c->status.as<unsigned long long>(),
+              next_epoch(c), err);
+  uint32_t t0, t1, t2;
+  group_tiles(G, t0, t1, t2);
+  e |= launch(c, MYYUV_K_COMPARE, k_decode_compare, dim3(t0 + t1 + t2, nf), dim3(kWave), s, in, d_size, cap,
+              (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, t0, t1,
+              c->qtd.as<const QTables>(), c->coef.as<uint4>(), static_cast<const uint8_t*>(d_ref), ref_fbytes,
+              c->mpart.as<uint4>(), d_map, err);
+  e |= launch_metric_reduce(c, G, d_out, s);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+// The host-buffer calls' last step: the records (and the map) come back.
+int compare_fetch(myyuv_hip_ctx* c, const FrameGeom& G, myyuv_frame_metric* out, myyuv_block_metric* map,
+                  hipStream_t s) {
+  myyuv_frame_metric m;
+  if (map && hipMemcpyAsync(map, c->mmap.p, (size_t)G.cum[3] * sizeof(myyuv_block_metric), hipMemcpyDeviceToHost,
+                            s) != hipSuccess)
+    return MYYUV_E_HIP;
+  if (d2h(&m, c->mrec.p, sizeof(m), s)) return MYYUV_E_HIP;
+  *out = m;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+}  // namespace
+
+double myyuv_metric_psnr(uint64_t sse, uint64_t nsamples) {
+  if (sse == 0) return HUGE_VAL;
+  return 10.0 * std::log10(65025.0 * (double)nsamples / (double)sse);
+}
+
+double myyuv_metric_ssim(int64_t ssim_sum, uint64_t nblocks) {
+  return (double)ssim_sum / ((double)nblocks * 16777216.0);
+}
+
+int myyuv_gpu_iyuv_compare(myyuv_hip_handle c, const uint8_t* ref, const uint8_t* test, uint32_t w, uint32_t h,
+                           myyuv_frame_metric* out, myyuv_block_metric* map) {
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!c || !ref || !test || !out) return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = make_geom(w, h, G);
+  if (e) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  if (c->frame.grow(G.fbytes) || c->mtest.grow(G.fbytes) || c->mrec.grow(sizeof(myyuv_frame_metric)) ||
+      (map && c->mmap.grow((size_t)G.cum[3] * sizeof(myyuv_block_metric))))
+    return MYYUV_E_HIP;
+  if (h2d(c->frame.p, ref, G.fbytes, s) || h2d(c->mtest.p, test, G.fbytes, s)) return MYYUV_E_HIP;
+  if ((e = launch_frame_compare(c, G, c->frame.p, 0, c->mtest.p, c->mrec.as<myyuv_frame_metric>(),
+                                map ? c->mmap.as<myyuv_block_metric>() : nullptr, s)))
+    return e;
+  return compare_fetch(c, G, out, map, s);
+}
+
+int myyuv_gpu_iyuv_compare_device(myyuv_hip_handle c, const void* d_ref, const void* d_test, uint32_t nframes,
+                                  uint32_t ref_frames, uint32_t w, uint32_t h, myyuv_frame_metric* d_out,
+                                  myyuv_block_metric* d_map, void* stream) {
+  if (!c || !d_ref || !d_test || !d_out || nframes == 0 || (ref_frames != 1 && ref_frames != nframes))
+    return MYYUV_E_ARG;
+  if (((uintptr_t)d_ref & 7) || ((uintptr_t)d_test & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_map & 7))
+    return MYYUV_E_ARG;
+  FrameGeom G;
+  int e;
+  if ((e = make_geom(w, h, G)) || (e = set_batch(G, nframes))) return e;
+  Entry en(c, stream);
+  // (the grid's 65,535 frames)
+  const uint32_t per = 65535u;
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    FrameGeom GL = G;
+    if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
+    const uint32_t rfb = ref_frames == 1 ? 0u : G.fbytes;
+    const uint8_t* rf = static_cast<const uint8_t*>(d_ref) + (size_t)f0 * rfb;
+    const uint8_t* tf = static_cast<const uint8_t*>(d_test) + (size_t)f0 * G.fbytes;
+    if ((e = launch_frame_compare(c, GL, rf, rfb, tf, d_out + f0, d_map ? d_map + (size_t)f0 * G.cum[3] : nullptr,
+                                  en.s)))
+      return e;
+  }
+  return 0;
+}
+
+int myyuv_gpu_dct_compare(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                          const uint8_t q[3], const uint8_t* ref_iyuv, myyuv_frame_metric* out,
+                          myyuv_block_metric* map, int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!c || !payload || !ref_iyuv || !out || !q) return MYYUV_E_ARG;
+  int e = check_q(q);
+  if (e) return e;
+  FrameGeom G;
+  if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const uint32_t cap = (size + 3) & ~3u;
+  if ((e = reserve_scaled(c, G)) || (e = set_qtables(c, q, s))) return e;
+  if (c->frame.grow(G.fbytes) || c->payload.grow(cap) || c->psize.grow(4) ||
+      c->mrec.grow(sizeof(myyuv_frame_metric)) ||
+      (map && c->mmap.grow((size_t)G.cum[3] * sizeof(myyuv_block_metric))))
+    return MYYUV_E_HIP;
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (hipMemsetAsync(static_cast<uint8_t*>(c->payload.p) + (cap - 4), 0, 4, s) != hipSuccess ||
+      h2d(c->payload.p, payload, size, s) || h2d(c->frame.p, ref_iyuv, G.fbytes, s) ||
+      hipMemcpyAsync(c->psize.p, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  if ((e = launch_dct_compare(c, G, c->payload.p, c->psize.as<const uint32_t>(), cap, c->frame.p, 0,
+                              c->mrec.as<myyuv_frame_metric>(), map ? c->mmap.as<myyuv_block_metric>() : nullptr,
+                              s)))
+    return e;
+  if ((e = read_err(c, s, bad_block))) {
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  return compare_fetch(c, G, out, map, s);
+}
+
+int myyuv_gpu_dct_compare_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_sizes, uint32_t cap,
+                                 uint32_t nframes, uint32_t w, uint32_t h, const uint8_t q[3], const void* d_ref,
+                                 uint32_t ref_frames, myyuv_frame_metric* d_out, myyuv_block_metric* d_map,
+                                 void* stream) {
+  if (!c || !d_payload || !d_sizes || !d_ref || !d_out || !q || (ref_frames != 1 && ref_frames != nframes))
+    return MYYUV_E_ARG;
+  if (((uintptr_t)d_payload & 3) || ((uintptr_t)d_ref & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_map & 7) ||
+      (nframes > 1 && (cap & 3)))
+    return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = check_q(q);
+  if (e || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes))) return e;
+  Entry en(c, stream);
+  // (as several launches past the kernels' 32-bit block numbers or the grid's 65,535 frames)
+  const uint32_t per = std::min(launch_frames(G, c->launch_blocks), 65535u);
+  FrameGeom GL = G;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve_scaled(c, GL)) || (e = set_qtables(c, q, en.s)))
+    return e;
+  const uint32_t rfb = ref_frames == 1 ? 0u : G.fbytes;
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GL.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
+    const uint8_t* pay = static_cast<const uint8_t*>(d_payload) + (size_t)f0 * cap;
+    const uint8_t* rf = static_cast<const uint8_t*>(d_ref) + (size_t)f0 * rfb;
+    if ((e = launch_dct_compare(c, GL, pay, d_sizes + f0, cap, rf, rfb, d_out + f0,
+                                d_map ? d_map + (size_t)f0 * G.cum[3] : nullptr, en.s)))
+      return e;
+  }
+  return 0;
+}
+
 // ---- requantise and transform (defined in myyuv_hip.h) ----------------------
 namespace {
 
@@ -1962,7 +2170,7 @@ int myyuv_gpu_dct_decompress_to_bmp_frames(myyuv_hip_handle c, const uint8_t* co
 }
 
 int myyuv_hip_profile(myyuv_hip_handle c, int enable) {
-  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_TOTAL) - 1u : 0u);
+  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_END) - 1u : 0u);
 }
 
 int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
@@ -1971,8 +2179,8 @@ int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
   DeviceGuard g(c->device);
   (void)hipStreamSynchronize(c->stream);
   drain_profile(c);
-  c->prof = mask & ((1u << MYYUV_K_TOTAL) - 1u);
-  for (int k = 0; k < MYYUV_K_TOTAL; k++) {
+  c->prof = mask & ((1u << MYYUV_K_END) - 1u);
+  for (int k = 0; k < MYYUV_K_END; k++) {
     c->ms[k] = 0;
     c->launches[k] = 0;
   }
@@ -1985,8 +2193,8 @@ int myyuv_hip_kernel_stats_n(myyuv_hip_handle c, uint32_t n, double* ms, int64_t
   DeviceGuard g(c->device);
   drain_profile(c);
   for (uint32_t k = 0; k < n; k++) {
-    ms[k] = k < MYYUV_K_TOTAL ? c->ms[k] : 0.0;
-    launches[k] = k < MYYUV_K_TOTAL ? c->launches[k] : 0;
+    ms[k] = k < MYYUV_K_END ? c->ms[k] : 0.0;
+    launches[k] = k < MYYUV_K_END ? c->launches[k] : 0;
   }
   return 0;
 }

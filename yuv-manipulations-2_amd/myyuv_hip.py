@@ -30,9 +30,16 @@ KERNELS = ["fdct_quant", "huff_encode", "scan_tiles", "stream_out", "encode_tile
 # KERNELS is the fixed-length list of myyuv_hip_kernel_stats (MYYUV_K_COUNT: part of that call's
 # ABI, it does not grow); ids from there on are read with myyuv_hip_kernel_stats_n, and
 # Codec.profile / Codec.kernel_stats take and return the names of KERNELS_ALL
-KERNELS_ALL = KERNELS + ["stream_gather"]
+KERNELS_ALL = KERNELS + ["stream_gather", "decode_compare", "frame_compare", "metric_reduce"]
 K_GATHER = KERNELS_ALL.index("stream_gather")
-K_TOTAL = len(KERNELS_ALL)  # MYYUV_K_TOTAL
+K_TOTAL = K_GATHER + 1  # MYYUV_K_TOTAL: frozen like MYYUV_K_COUNT; the ids after it end at K_END
+K_COMPARE = KERNELS_ALL.index("decode_compare")
+K_FRAME_CMP = KERNELS_ALL.index("frame_compare")
+K_METRIC_SUM = KERNELS_ALL.index("metric_reduce")
+K_END = len(KERNELS_ALL)  # MYYUV_K_END
+# myyuv_block_metric, as the maps of the compare calls come back
+BLOCK_METRIC = np.dtype([("sse", np.uint32), ("ssim", np.int32)])
+SSIM_ONE = 1 << 24  # ssim of identical blocks
 # MYYUV_XF_*: bit 0 mirror x, bit 1 mirror y, bit 2 swap (transpose first, then the mirrors)
 (XF_NONE, XF_FLIP_H, XF_FLIP_V, XF_ROT180, XF_TRANSPOSE, XF_ROT90, XF_ROT270, XF_TRANSVERSE) = range(8)
 XF_NAMES = {"none": 0, "flip_h": 1, "flip_v": 2, "rot180": 3, "transpose": 4, "rot90": 5, "rot270": 6,
@@ -62,7 +69,24 @@ EXPORTS = [
     "myyuv_gpu_dct_requantize", "myyuv_gpu_dct_requantize_device",
     "myyuv_gpu_dct_transform", "myyuv_gpu_dct_transform_device",
     "myyuv_gpu_dct_crop", "myyuv_gpu_dct_crop_device", "myyuv_gpu_dct_join", "myyuv_gpu_dct_join_device",
+    "myyuv_metric_psnr", "myyuv_metric_ssim", "myyuv_gpu_iyuv_compare", "myyuv_gpu_iyuv_compare_device",
+    "myyuv_gpu_dct_compare", "myyuv_gpu_dct_compare_device",
 ]
+
+
+class PlaneMetric(ctypes.Structure):
+    """myyuv_plane_metric"""
+    _fields_ = [("sse", ctypes.c_uint64), ("ssim_sum", ctypes.c_int64), ("nblocks", ctypes.c_uint32),
+                ("max_abs", ctypes.c_uint32)]
+
+
+class FrameMetric(ctypes.Structure):
+    """myyuv_frame_metric"""
+    _fields_ = [("plane", PlaneMetric * 3)]
+
+    def as_ints(self):
+        """((sse, ssim_sum, nblocks, max_abs) of Y, of U, of V), plain ints."""
+        return tuple((int(p.sse), int(p.ssim_sum), int(p.nblocks), int(p.max_abs)) for p in self.plane)
 
 _lib = None
 # myyuv_payload_alloc_fn
@@ -165,6 +189,15 @@ def load():
     L.myyuv_gpu_dct_join.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u32), u32, u32, u32, u32, u8p, u32,
                                      ctypes.POINTER(u32), i64p]
     L.myyuv_gpu_dct_join_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, vp, u32, vp, vp]
+    fmp = ctypes.POINTER(FrameMetric)
+    L.myyuv_metric_psnr.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    L.myyuv_metric_psnr.restype = ctypes.c_double
+    L.myyuv_metric_ssim.argtypes = [ctypes.c_int64, ctypes.c_uint64]
+    L.myyuv_metric_ssim.restype = ctypes.c_double
+    L.myyuv_gpu_iyuv_compare.argtypes = [vp, u8p, u8p, u32, u32, fmp, vp]
+    L.myyuv_gpu_iyuv_compare_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
+    L.myyuv_gpu_dct_compare.argtypes = [vp, u8p, u32, u32, u32, u8p, u8p, fmp, vp, i64p]
+    L.myyuv_gpu_dct_compare_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, vp, u32, vp, vp, vp]
     L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -181,6 +214,16 @@ def strerror(code):
 
 def payload_bound(w, h):
     return load().myyuv_dct_payload_bound(w, h)
+
+
+def metric_psnr(sse, nsamples):
+    """myyuv_metric_psnr: dB, inf at sse == 0."""
+    return load().myyuv_metric_psnr(int(sse), int(nsamples))
+
+
+def metric_ssim(ssim_sum, nblocks):
+    """myyuv_metric_ssim: ssim_sum / (nblocks * 2^24)."""
+    return load().myyuv_metric_ssim(int(ssim_sum), int(nblocks))
 
 
 def k2_constants():
@@ -545,6 +588,62 @@ class Codec:
             raise CodecError(rc, bad.value)
         return out[:n].tobytes()
 
+    # -- compare: PSNR's and block SSIM's integers between two frames, or between a
+    # DCT stream and a frame without decoding it to memory (defined in include/myyuv_hip.h) --
+    def compare_frames(self, ref, test, w, h, want_map=False):
+        """Two raw IYUV frames -> ((sse, ssim_sum, nblocks, max_abs) of Y, U, V)
+        as plain ints; with want_map also the per-block map (a BLOCK_METRIC
+        array in the codec's block order, planes Y U V)."""
+        a = np.ascontiguousarray(np.frombuffer(memoryview(ref).cast("B"), np.uint8))
+        b = np.ascontiguousarray(np.frombuffer(memoryview(test).cast("B"), np.uint8))
+        fb = int(w) * int(h) * 3 // 2
+        if a.size < fb or b.size < fb:
+            raise ValueError("frame smaller than W*H*3/2")
+        out = FrameMetric()
+        bmap = np.zeros(max(1, (w // 8) * (h // 8) + 2 * (w // 16) * (h // 16)), BLOCK_METRIC) if want_map else None
+        rc = load().myyuv_gpu_iyuv_compare(self._h, _u8(a), _u8(b), w, h, ctypes.byref(out),
+                                           bmap.ctypes.data if want_map else None)
+        if rc:
+            raise CodecError(rc)
+        return (out.as_ints(), bmap) if want_map else out.as_ints()
+
+    def compare_stream(self, payload, w, h, q, ref, want_map=False):
+        """A DCTYUV payload against a raw IYUV frame, as compare_frames; the
+        payload's decoded frame is never written."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        a = np.ascontiguousarray(np.frombuffer(memoryview(ref).cast("B"), np.uint8))
+        if a.size < int(w) * int(h) * 3 // 2:
+            raise ValueError("frame smaller than W*H*3/2")
+        out = FrameMetric()
+        bmap = np.zeros(max(1, (w // 8) * (h // 8) + 2 * (w // 16) * (h // 16)), BLOCK_METRIC) if want_map else None
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_compare(self._h, _u8(src), src.size, w, h, _u8(_q(q)), _u8(a), ctypes.byref(out),
+                                          bmap.ctypes.data if want_map else None, ctypes.byref(bad))
+        if rc:
+            e = CodecError(rc, bad.value)
+            e.metric = out.as_ints()  # (left zeroed by the call)
+            raise e
+        return (out.as_ints(), bmap) if want_map else out.as_ints()
+
+    def compare_frames_device(self, d_ref, d_test, nframes, ref_frames, w, h, d_out, d_map=None, stream=None):
+        """Device-resident batch of compare_frames: test frame f against
+        reference frame f (ref_frames == nframes) or the one frame at d_ref
+        (ref_frames == 1) -> d_out[f] (myyuv_frame_metric, 72 B) and the map at
+        d_map when given; asynchronous."""
+        rc = load().myyuv_gpu_iyuv_compare_device(self._h, d_ref, d_test, nframes, ref_frames, w, h, d_out, d_map,
+                                                  stream)
+        if rc:
+            raise CodecError(rc)
+
+    def compare_stream_device(self, d_payload, d_sizes, cap, nframes, w, h, q, d_ref, ref_frames, d_out, d_map=None,
+                              stream=None):
+        """Device-resident batch of compare_stream: stream f at d_payload +
+        f*cap; asynchronous, errors through sync_status."""
+        rc = load().myyuv_gpu_dct_compare_device(self._h, d_payload, d_sizes, cap, nframes, w, h, _u8(_q(q)), d_ref,
+                                                 ref_frames, d_out, d_map, stream)
+        if rc:
+            raise CodecError(rc)
+
     # -- requantise: a DCT stream re-encoded at another quality on its coefficients,
     # no pixels in between (defined in include/myyuv_hip.h) --
     def requantize(self, payload, w, h, q_src, q_dst):
@@ -738,12 +837,12 @@ class Codec:
 
     def kernel_stats(self):
         """{name: (summed ms, launches)} for every name of KERNELS_ALL."""
-        ms = (ctypes.c_double * K_TOTAL)()
-        n = (ctypes.c_int64 * K_TOTAL)()
-        rc = load().myyuv_hip_kernel_stats_n(self._h, K_TOTAL, ms, n)
+        ms = (ctypes.c_double * K_END)()
+        n = (ctypes.c_int64 * K_END)()
+        rc = load().myyuv_hip_kernel_stats_n(self._h, K_END, ms, n)
         if rc:
             raise CodecError(rc)
-        return {KERNELS_ALL[i]: (ms[i], n[i]) for i in range(K_TOTAL)}
+        return {KERNELS_ALL[i]: (ms[i], n[i]) for i in range(K_END)}
 
     def tinfo_guard(self, ntiles, arm):
         """Diagnostic (not in include/myyuv_hip.h): arm=True writes a canary
