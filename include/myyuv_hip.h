@@ -66,6 +66,11 @@ typedef struct myyuv_hip_ctx* myyuv_hip_handle;
 int myyuv_hip_create(int device, myyuv_hip_handle* out);
 void myyuv_hip_destroy(myyuv_hip_handle h);
 const char* myyuv_hip_strerror(int code);
+/* The text of every code.  myyuv_hip_strerror's table is closed at code 17
+ * (its callers were built against "Unknown error" for everything above);
+ * codes added since have their text here, and the codes up to 17 give
+ * myyuv_hip_strerror's.  New callers use this one. */
+const char* myyuv_hip_error_message(int code);
 
 /* Upper bound of the DCTYUV payload for a WxH IYUV frame (worst-case 160 B per
  * 8x8 block + headers); size the compress output buffer with it. */
@@ -705,6 +710,102 @@ int myyuv_gpu_dct_compare_device(myyuv_hip_handle h, const void* d_payload, cons
                                  const uint8_t quality[3], const void* d_ref, uint32_t ref_frames,
                                  myyuv_frame_metric* d_out, myyuv_block_metric* d_map_or_null, void* stream);
 
+/* Probe: what a quality triple would cost and what it would give, without a
+ * stream being written.
+ *   MYYUV_PROBE_SIZE    K1 (+ its exact path) -> K2 (+ overflow tiers) -> the
+ *     tile scan; the stream writer does not run.  plane_bytes[p] is the
+ *     stream's plane_size[p] (8 + blocks + content), payload_bytes = 12 + their
+ *     sum: exactly *payload_size of myyuv_gpu_dct_compress at that quality.
+ *   MYYUV_PROBE_METRIC  K1 (+ its exact path) -> coef_compare -> metric_reduce;
+ *     no Huffman stage runs.  coef_compare is K6's transform over the
+ *     coefficient image K1 leaves in the workspace, with the source frame's
+ *     rows loaded where K6 stores its own.  `metric` (and the map) is exactly
+ *     what myyuv_gpu_dct_compare reports for that payload against `iyuv`.
+ * With both bits K1 runs once.  The fields of a part that was not asked for
+ * are zero; every record is written whole by every call.  Checks: those of
+ * myyuv_gpu_dct_compress, in its order, then `what` in {1, 2, 3}
+ * (MYYUV_E_ARG).  Under MYYUV_ENCODER=fused the size part runs the fused
+ * encoder and the metric part K1 and its exact path all the same (the fused
+ * encoder leaves no coefficient image to rely on). */
+#define MYYUV_PROBE_SIZE 1u
+#define MYYUV_PROBE_METRIC 2u
+typedef struct {
+  uint32_t plane_bytes[3];
+  uint32_t payload_bytes;
+  myyuv_frame_metric metric;
+} myyuv_probe; /* 88 B */
+int myyuv_gpu_dct_probe(myyuv_hip_handle h, const uint8_t* iyuv, uint32_t width, uint32_t height,
+                        const uint8_t quality[3], uint32_t what, myyuv_probe* out,
+                        myyuv_block_metric* map_or_null);
+/* Device-resident batch: frame f at d_iyuv + f*W*H*3/2 -> d_out[f], and
+ * d_map[f * blocks_per_frame + g] when d_map is not null and the metric part
+ * is asked for; asynchronous on `stream` (NULL = the context's).  d_iyuv,
+ * d_out and d_map are 8-byte aligned.  Argument errors are returned at once. */
+int myyuv_gpu_dct_probe_device(myyuv_hip_handle h, const void* d_iyuv, uint32_t nframes, uint32_t width,
+                               uint32_t height, const uint8_t quality[3], uint32_t what, myyuv_probe* d_out,
+                               myyuv_block_metric* d_map_or_null, void* stream);
+
+/* Encode to a target: a byte budget, or a squared-error ceiling per plane.
+ * The search (yuv-manipulations-2_amd/csrc/rate_search.h, plain C++, shared
+ * with the host check) probes qualities and is defined here bit for bit; it
+ * is this bisection, not "the best quality" (sizes and errors are not always
+ * monotone in the quality).  mid = (lo + hi) / 2, integer division.
+ *
+ * Size: one quality q for the three planes, budget B payload bytes.
+ *   1. probe 100; size(100) <= B: the result is 100.
+ *   2. probe 1; size(1) > B: MYYUV_E_TARGET, the probe at 1 reported.
+ *   3. lo = 1, hi = 100; while hi - lo > 1: size(mid) <= B ? lo = mid : hi = mid.
+ *      The result is lo.
+ * At most 9 probes; size(q) <= B and (q == 100 or size(q + 1) > B).
+ *
+ * Distortion: per plane p the ceiling max_sse[p]; plane p "meets" at a probe
+ * when its sse <= max_sse[p].
+ *   1. probe (100, 100, 100); a plane that does not meet fails the call:
+ *      MYYUV_E_TARGET, bit p of failed_planes set, the probe at 100 reported.
+ *   2. probe (1, 1, 1); a plane that meets gets 1.
+ *   3. every other plane: lo = 1, hi = 100; while hi - lo > 1: the plane meets
+ *      at mid ? hi = mid : lo = mid.  The result is hi.
+ * The planes bisect in lockstep: a probe carries each plane's current mid, a
+ * finished plane its result; at most 9 probes serve the three planes.
+ *
+ * After the search one ordinary compress at the chosen qualities writes the
+ * payload: byte for byte myyuv_gpu_dct_compress at result->quality.
+ * result->quality holds the chosen qualities, or under MYYUV_E_TARGET those
+ * of the failing probe, when `payload` and `*payload_size` are left
+ * untouched.  result->at is the probe of result->quality with both parts:
+ * the part the search steers by as its probes reported it (every chosen
+ * quality was probed), the other part from one launch after the search.
+ * result->probes counts the search's probes.  Checks: those
+ * of myyuv_gpu_dct_compress (result among the pointers; no quality).  The
+ * frame goes to the device once.  The search reads 88 B back per step, so the
+ * _device forms block until the payload is written, unlike every other device
+ * call here: the chosen quality is a host-side result.  d_iyuv is 8-byte,
+ * d_payload 4-byte aligned; *d_payload_size is written on the device. */
+#define MYYUV_E_TARGET 18 /* "target not reachable" (no reference counterpart; myyuv_hip_error_message) */
+typedef struct {
+  uint8_t quality[3];
+  uint8_t failed_planes;
+  uint32_t probes;
+  myyuv_probe at;
+} myyuv_target_result;
+int myyuv_gpu_dct_compress_to_size(myyuv_hip_handle h, const uint8_t* iyuv, uint32_t width, uint32_t height,
+                                   uint32_t max_payload_bytes, uint8_t* payload, uint32_t cap,
+                                   uint32_t* payload_size, myyuv_target_result* result);
+int myyuv_gpu_dct_compress_to_sse(myyuv_hip_handle h, const uint8_t* iyuv, uint32_t width, uint32_t height,
+                                  const uint64_t max_sse[3], uint8_t* payload, uint32_t cap,
+                                  uint32_t* payload_size, myyuv_target_result* result);
+int myyuv_gpu_dct_compress_to_size_device(myyuv_hip_handle h, const void* d_iyuv, uint32_t width, uint32_t height,
+                                          uint32_t max_payload_bytes, void* d_payload, uint32_t cap,
+                                          uint32_t* d_payload_size, myyuv_target_result* result, void* stream);
+int myyuv_gpu_dct_compress_to_sse_device(myyuv_hip_handle h, const void* d_iyuv, uint32_t width, uint32_t height,
+                                         const uint64_t max_sse[3], void* d_payload, uint32_t cap,
+                                         uint32_t* d_payload_size, myyuv_target_result* result, void* stream);
+/* The largest s with myyuv_metric_psnr(s, nsamples) >= db (by the formula,
+ * then stepped against myyuv_metric_psnr itself): db <= 0 gives
+ * 65025 * nsamples, +inf gives 0.  NaN gives 0 here; the callers that take a
+ * dB figure reject it (MYYUV_E_ARG). */
+uint64_t myyuv_metric_sse_for_psnr(double db, uint64_t nsamples);
+
 /* Host-buffer batches (many frames per call; §7 step 9:
  * transfers overlapped with the kernels).  The batch runs in chunks of up to
  * 8 frames through two device slots: chunk k's host -> device copies, chunk
@@ -784,12 +885,17 @@ int myyuv_hip_sync_status(myyuv_hip_handle h, void* stream, int64_t* bad_block);
 #define MYYUV_K_GATHER 17    /* byte gather of crop and join, wave per run (stream_gather) */
 #define MYYUV_K_TOTAL 18     /* every id above is below this */
 /* MYYUV_K_TOTAL is frozen as MYYUV_K_COUNT is (callers size their arrays for
- * myyuv_hip_kernel_stats_n with it).  Later ids follow it; MYYUV_K_END is the
- * bound of all ids, and the length to pass for all of them. */
+ * myyuv_hip_kernel_stats_n with it).  Later ids follow it, up to MYYUV_K_END. */
 #define MYYUV_K_COMPARE 18   /* fused decoder against a reference frame (decode_compare) */
 #define MYYUV_K_FRAME_CMP 19 /* two raw frames against each other (frame_compare) */
 #define MYYUV_K_METRIC_SUM 20 /* the compare kernels' per-group totals summed per plane (metric_reduce) */
-#define MYYUV_K_END 21       /* every id is below this */
+#define MYYUV_K_END 21       /* every id above is below this */
+/* MYYUV_K_END is frozen as the two bounds before it (callers size their arrays
+ * with it too).  The probe's ids follow it; MYYUV_K_LIMIT is the bound of all
+ * ids, and the length to pass to myyuv_hip_kernel_stats_n for all of them. */
+#define MYYUV_K_COEF_CMP 21  /* K6's transform of K1's coefficient image against the source frame (coef_compare) */
+#define MYYUV_K_PROBE_OUT 22 /* a probe's sizes and plane records gathered into its myyuv_probe records (probe_out) */
+#define MYYUV_K_LIMIT 23     /* every id is below this */
 int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 /* As myyuv_hip_profile, but stamps only the kernels whose bit (1 << MYYUV_K_*)
  * is set in `mask` (0 disables): event stamping costs host and queue time per
@@ -797,8 +903,8 @@ int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 int myyuv_hip_profile_kernels(myyuv_hip_handle h, uint32_t mask);
 int myyuv_hip_kernel_stats(myyuv_hip_handle h, double ms[MYYUV_K_COUNT],
                            int64_t launches[MYYUV_K_COUNT]);
-/* The same for the first min(n, MYYUV_K_END) ids; entries from
- * MYYUV_K_END on, if any, are set to 0. */
+/* The same for the first min(n, MYYUV_K_LIMIT) ids; entries from
+ * MYYUV_K_LIMIT on, if any, are set to 0. */
 int myyuv_hip_kernel_stats_n(myyuv_hip_handle h, uint32_t n, double* ms, int64_t* launches);
 
 /* Block-level entry points for known-answer tests (device round trip of one

@@ -40,6 +40,13 @@
 // include/myyuv_hip.h: PSNR and 8x8-block SSIM per plane, on the GPU; a
 // compressed side against a raw one is never decoded to memory):
 //   myyuv_cli a.myyuv -compare b.myyuv [-o report.txt]
+// the quality found for a target instead of given (probe and encode to a
+// target, include/myyuv_hip.h: BYTES is the output file's size; each prints
+// `quality Y U V : size N : psnr y u v dB : P probes` first), and what given
+// qualities would cost and give, nothing written:
+//   myyuv_cli in.myyuv -compress DCT -target_size BYTES -o out.myyuv
+//   myyuv_cli in.myyuv -compress DCT -target_psnr DB -o out.myyuv
+//   myyuv_cli in.myyuv -probe q [q [q]]
 // and, beyond the reference CLI, many frames per invocation (SURVEY.md §8f
 // row 2; frames of one geometry share batched kernel launches):
 //   myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IN.myyuv...
@@ -73,6 +80,11 @@ void usage() {
             << "Usage:\n"
             << "  myyuv_cli IMAGE.myyuv -info\n"
             << "  myyuv_cli IMAGE.myyuv -compress DCT Q [Q [Q]] -o OUT.myyuv   (Q in 1..100, per plane Y U V)\n"
+            << "  myyuv_cli IMAGE.myyuv -compress DCT -target_size BYTES -o OUT.myyuv\n"
+            << "  myyuv_cli IMAGE.myyuv -compress DCT -target_psnr DB -o OUT.myyuv\n"
+            << "      (the quality found on the GPU: OUT.myyuv of at most BYTES, or every plane at least DB dB)\n"
+            << "  myyuv_cli IMAGE.myyuv -probe Q [Q [Q]]\n"
+            << "      (the size and the PSNR those qualities would give; nothing is written)\n"
             << "  myyuv_cli IMAGE.myyuv -decompress [-crop X Y W H] -o OUT.myyuv\n"
             << "  myyuv_cli IMAGE.myyuv -to_bmp [24|32] [-chroma nearest|linear] [-crop X Y W H] -o OUT.bmp\n"
             << "      (-crop: only that region, luma pixels from the top-left, multiples of 16)\n"
@@ -212,6 +224,84 @@ std::string compare_report(const myyuv::YUV& a, const myyuv::YUV& b) {
   return text;
 }
 
+// `quality Y U V : size N : psnr y u v dB : P probes` of a probe record: N the
+// .myyuv file's size at those qualities (64-byte header, 3 parameter bytes,
+// the payload), the planes' PSNR as -compare prints it.
+std::string target_line(const uint8_t q[3], const myyuv_probe& at, uint32_t w, uint32_t h, uint32_t probes) {
+  const uint64_t samples[3] = {(uint64_t)w * h, (uint64_t)w * h / 4, (uint64_t)w * h / 4};
+  std::string text = "quality " + std::to_string(q[0]) + " " + std::to_string(q[1]) + " " + std::to_string(q[2]) +
+                     " : size " + std::to_string((uint64_t)at.payload_bytes + sizeof(myyuv::YUVHeader) + 3) + " : psnr";
+  for (int p = 0; p < 3; p++) {
+    char t[64];
+    if (at.metric.plane[p].sse == 0)
+      std::snprintf(t, sizeof t, " inf");
+    else
+      std::snprintf(t, sizeof t, " %.6f", myyuv_metric_psnr(at.metric.plane[p].sse, samples[p]));
+    text += t;
+  }
+  return text + " dB : " + std::to_string(probes) + " probes\n";
+}
+
+constexpr const char* kTargetHelp =
+    "Invalid argument, -target_size BYTES or -target_psnr DB must be followed by `-o /path/to/new_image.myyuv`\n";
+
+// `-compress DCT -target_size BYTES -o OUT` / `-target_psnr DB -o OUT` at
+// args[a]: BYTES is the output file's size (header and parameter bytes
+// included).  A target out of reach: one fixed line, exit 1, no file.
+int run_target(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& args) {
+  const bool by_size = args[a] == "-target_size";
+  if (args.size() != a + 4 || args[a + 2] != "-o") {
+    std::cout << kTargetHelp;
+    usage();
+    return 1;
+  }
+  const std::string& v = args[a + 1];
+  uint32_t budget = 0;
+  double db = 0;
+  if (by_size) {
+    if (v.empty() || v.size() > 10 || v.find_first_not_of("0123456789") != std::string::npos) {
+      std::cout << kTargetHelp;
+      usage();
+      return 1;
+    }
+    const unsigned long long bytes = std::stoull(v), head = sizeof(myyuv::YUVHeader) + 3;
+    budget = bytes < head ? 0u : (bytes - head > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(bytes - head));
+  } else {
+    size_t used = 0;
+    try {
+      db = std::stod(v, &used);
+    } catch (const std::exception&) {
+      used = 0;
+    }
+    if (used != v.size() || db != db) {
+      std::cout << kTargetHelp;
+      usage();
+      return 1;
+    }
+  }
+  myyuv::YUV out;
+  myyuv_target_result res;
+  std::memset(&res, 0, sizeof(res));
+  bool unreachable = false;
+  const float ms = elapsed_ms([&] {
+    try {
+      out = by_size ? yuv.compress_to_size(budget, &res) : yuv.compress_to_psnr(db, &res);
+    } catch (const std::runtime_error& e) {
+      if (std::string(e.what()) != myyuv_hip_error_message(MYYUV_E_TARGET)) throw;
+      unreachable = true;
+    }
+  });
+  if (unreachable) {
+    std::cout << "Error compressing: " << myyuv_hip_error_message(MYYUV_E_TARGET) << '\n';
+    return 1;
+  }
+  std::cout << target_line(res.quality, res.at, yuv.getWidth(), yuv.getHeight(), res.probes);
+  std::cout << "YUV DCT compression (" << (by_size ? " -target_size " : " -target_psnr ") << v << " ) : " << ms
+            << " ms\n";
+  out.dump(args[a + 3]);
+  return 0;
+}
+
 int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& args_in) {
   std::vector<std::string> args = args_in;
   const std::string cmd = args[a];
@@ -249,6 +339,7 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     }
     const std::string algo = args[a++];
     if (algo != "DCT") throw std::runtime_error("Compression not registered: " + algo);
+    if (a < args.size() && (args[a] == "-target_size" || args[a] == "-target_psnr")) return run_target(yuv, a, args);
     std::vector<std::string> params;
     while (a < args.size() && args[a] != "-o") params.push_back(args[a++]);
     a++;
@@ -263,6 +354,16 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     const float ms = elapsed_ms([&] { out = compress_dct(yuv, params); });
     std::cout << "YUV DCT compression (" << label << ") : " << ms << " ms\n";
     out.dump(args[a]);
+    return 0;
+  }
+  if (cmd == "-probe") {  // Q [Q [Q]]: what those qualities would cost and give, nothing written
+    const std::vector<std::string> params(args.begin() + a + 1, args.end());
+    uint8_t q[3];
+    dct_qualities(params, q);
+    myyuv_probe at;
+    const float ms = elapsed_ms([&] { at = yuv.probe({q[0], q[1], q[2]}); });
+    std::cout << target_line(q, at, yuv.getWidth(), yuv.getHeight(), 1);
+    std::cout << "YUV DCT probe : " << ms << " ms\n";
     return 0;
   }
   if (cmd == "-requantize") {  // Q [Q [Q]] -o OUT.myyuv: the qualities as -compress DCT's

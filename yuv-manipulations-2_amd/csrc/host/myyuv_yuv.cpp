@@ -37,7 +37,7 @@ struct ThreadCodec {
 };
 thread_local ThreadCodec t_codec;
 
-[[noreturn]] void fail(int rc) { throw std::runtime_error(myyuv_hip_strerror(rc)); }
+[[noreturn]] void fail(int rc) { throw std::runtime_error(myyuv_hip_error_message(rc)); }
 
 uint8_t* dup(const uint8_t* src, size_t n) {
   if (!src) return nullptr;
@@ -464,6 +464,69 @@ myyuv_frame_metric YUV::compare(const YUV& other, std::vector<myyuv_block_metric
   if (rc) fail(rc);
   if (map) map->resize(nblk);
   return out;
+}
+
+// Probe and encode to a target (include/myyuv_hip.h).
+namespace {
+
+void raw_planar_ok(const YUV& y) {
+  if (y.getFormatGroup() != YUV::FormatGroup::PLANAR) throw std::runtime_error("Error compressing: YUV must be planar");
+  if (y.getCompression() != YUV::Compressions::NONE)
+    throw std::runtime_error("Error compressing: can't compress uncompressed YUV");
+}
+
+// compress_DCT_planar's result from a payload and its three quality bytes
+YUV compressed_like(const YUV& yuv, const uint8_t q[3], const uint8_t* payload, uint32_t size) {
+  YUV res;
+  res.header = yuv.header;
+  res.header.compression = YUV::Compressions::DCT;
+  res.header.compression_params_size = 3;
+  res.header.compression_params_pos = sizeof(YUVHeader);
+  res.header.data_pos = sizeof(YUVHeader) + 3;
+  res.header.data_size = size;
+  res.compression_params = new uint8_t[3]{q[0], q[1], q[2]};
+  res.data = new uint8_t[size];
+  std::memcpy(res.data, payload, size);
+  return res;
+}
+
+}  // namespace
+
+myyuv_probe YUV::probe(const std::array<uint8_t, 3>& q) const {
+  raw_planar_ok(*this);
+  myyuv_probe out;
+  const int rc = myyuv_gpu_dct_probe(t_codec.get(), data, header.width, header.height, q.data(),
+                                     MYYUV_PROBE_SIZE | MYYUV_PROBE_METRIC, &out, nullptr);
+  if (rc) fail(rc);
+  return out;
+}
+
+YUV YUV::compress_to_size(uint32_t payload_bytes, myyuv_target_result* result) const {
+  raw_planar_ok(*this);
+  std::vector<uint8_t> payload(myyuv_dct_payload_bound(header.width, header.height));
+  uint32_t size = 0;
+  myyuv_target_result r;
+  const int rc = myyuv_gpu_dct_compress_to_size(t_codec.get(), data, header.width, header.height, payload_bytes,
+                                                payload.data(), (uint32_t)payload.size(), &size, &r);
+  if (result) *result = r;
+  if (rc) fail(rc);
+  return compressed_like(*this, r.quality, payload.data(), size);
+}
+
+YUV YUV::compress_to_psnr(double db, myyuv_target_result* result) const {
+  raw_planar_ok(*this);
+  if (db != db) fail(MYYUV_E_ARG);
+  const uint64_t n = (uint64_t)header.width * header.height;
+  const uint64_t max_sse[3] = {myyuv_metric_sse_for_psnr(db, n), myyuv_metric_sse_for_psnr(db, n / 4),
+                               myyuv_metric_sse_for_psnr(db, n / 4)};
+  std::vector<uint8_t> payload(myyuv_dct_payload_bound(header.width, header.height));
+  uint32_t size = 0;
+  myyuv_target_result r;
+  const int rc = myyuv_gpu_dct_compress_to_sse(t_codec.get(), data, header.width, header.height, max_sse,
+                                               payload.data(), (uint32_t)payload.size(), &size, &r);
+  if (result) *result = r;
+  if (rc) fail(rc);
+  return compressed_like(*this, r.quality, payload.data(), size);
 }
 
 }  // namespace myyuv

@@ -103,6 +103,17 @@ class YUV {
   // of different size or format: std::runtime_error("Error comparing: the
   // frames differ in size or format").
   myyuv_frame_metric compare(const YUV& other, std::vector<myyuv_block_metric>* map = nullptr) const;
+  // Probe and encode to a target (include/myyuv_hip.h) of an uncompressed
+  // planar frame.  probe: what the qualities q would cost and give, both
+  // parts, no stream written.  compress_to_size: the compressed frame the size
+  // bisection finds for a budget of payload_bytes; compress_to_psnr: the one
+  // whose every plane keeps at least db dB (NaN: std::runtime_error).  The
+  // result's three parameter bytes are the chosen qualities; *result, when
+  // given, is filled on success and on failure.  A target out of reach:
+  // std::runtime_error("target not reachable").
+  myyuv_probe probe(const std::array<uint8_t, 3>& q) const;
+  YUV compress_to_size(uint32_t payload_bytes, myyuv_target_result* result = nullptr) const;
+  YUV compress_to_psnr(double db, myyuv_target_result* result = nullptr) const;
   void load(const std::string& path);
   void load(const BMP& bmp, FourccFormat format);
   void dump(const std::string& path) const;

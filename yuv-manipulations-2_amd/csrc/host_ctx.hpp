@@ -79,6 +79,10 @@ __global__ void k_decode_compare(const uint8_t*, const uint32_t*, uint32_t, cons
 __global__ void k_frame_compare(const uint8_t*, uint32_t, const uint8_t*, FrameGeom, uint32_t, uint32_t, uint4*,
                                 myyuv_block_metric*);
 __global__ void k_metric_reduce(const uint4*, uint32_t, uint32_t, uint32_t, myyuv_frame_metric*);
+__global__ void k_coef_compare(const uint4*, const uint8_t*, const uint4*, FrameGeom, const QTables*, const uint8_t*,
+                               uint4*, myyuv_block_metric*, uint4*);
+__global__ void k_probe_out(const uint32_t*, const uint32_t*, const myyuv_frame_metric*, uint32_t, uint32_t,
+                            myyuv_probe*);
 template <int BPP>
 __global__ void k_bmp_to_iyuv(const uint8_t*, uint32_t, uint32_t, uint32_t, uint8_t*);
 template <int BPP, int LINEAR>
@@ -172,7 +176,8 @@ struct myyuv_hip_ctx {
   // fix_list, codec_common.hpp; fix_par alternates from launch to launch)
   DevBuf fix;
   uint32_t fix_par = 0;
-  uint32_t xf_resident[2] = {kXfWaves / 4, kXfWaves / 4};  // K1, K6 workgroups resident on the device
+  // K1, K6, k_coef_compare workgroups resident on the device
+  uint32_t xf_resident[3] = {kXfWaves / 4, kXfWaves / 4, kXfWaves / 4};
   uint32_t fix_resident = kXfWaves / 4;                      // k_fdct_fix workgroups resident
   // k_fdct_fix's grid at qualities up to fix_qmax (MYYUV_FIX_GRID; 0, the
   // default: the resident count, as above fix_qmax).  A small fixed grid
@@ -223,6 +228,10 @@ struct myyuv_hip_ctx {
   // the per-block map and the staged test frame (the reference frame is
   // staged in `frame`)
   DevBuf mpart, mrec, mmap, mtest;
+  // probe: per frame the 12 stream-head bytes and the payload size the tile
+  // scan writes, then an error word of its own (the scan reports a head-only
+  // capacity as an overflow; nobody reads it); the host-buffer calls' records
+  DevBuf pbsz, prec;
   // profiling: the kernels' start/stop events until drain_profile reads
   // them; they are used again from launch to launch
   struct Stamp {
@@ -231,8 +240,8 @@ struct myyuv_hip_ctx {
   };
   uint32_t prof = 0;  // bit k: stamp kernel id k
   uint32_t skip = 0;  // diagnostic: bit k: do not launch kernel id k (myyuv_debug_skip_kernels)
-  double ms[MYYUV_K_END] = {};
-  int64_t launches[MYYUV_K_END] = {};
+  double ms[MYYUV_K_LIMIT] = {};
+  int64_t launches[MYYUV_K_LIMIT] = {};
   std::vector<Stamp> pending;
   std::vector<Event> free_events;
   // set once every piece of it exists (pipe_init)

@@ -360,12 +360,23 @@ __global__ __launch_bounds__(256) void k_metric_reduce(const uint4* __restrict__
   unsigned long long sse = 0;
   long long ss = 0;
   uint32_t n = 0, mx = 0;
-  for (uint32_t i = threadIdx.x; i < cnt; i += 256u) {
-    const uint4 v = src[i];
-    sse += v.x;
-    ss += (int32_t)v.y;
-    n += v.z;
-    mx = max(mx, v.w);
+  // eight totals per thread and round, loaded unconditionally (slots past the
+  // end read the round's first) so that all eight loads are in flight together:
+  // one dependent load per round took 82 us for the 98,304 unit totals of an
+  // 8192x8192 probe (profiles/target_rate.json)
+  constexpr uint32_t kBatch = 8;
+  for (uint32_t i0 = threadIdx.x; i0 < cnt; i0 += 256u * kBatch) {
+    uint4 v[kBatch];
+#pragma unroll
+    for (uint32_t k = 0; k < kBatch; k++) v[k] = src[i0 + 256u * k < cnt ? i0 + 256u * k : i0];
+#pragma unroll
+    for (uint32_t k = 0; k < kBatch; k++) {
+      if (i0 + 256u * k >= cnt) continue;
+      sse += v[k].x;
+      ss += (int32_t)v[k].y;
+      n += v[k].z;
+      mx = max(mx, v[k].w);
+    }
   }
   __shared__ unsigned long long s_sse[256];
   __shared__ long long s_ss[256];
@@ -392,6 +403,26 @@ __global__ __launch_bounds__(256) void k_metric_reduce(const uint4* __restrict__
     r.max_abs = s_mx[0];
     out[f].plane[p] = r;
   }
+}
+
+// k_probe_out: a probe's records (include/myyuv_hip.h, "Probe"), one thread
+// per frame.  heads: the 12 bytes k_tile_scan writes at a stream's start (the
+// three plane sizes) per frame, sizes: its payload sizes, rec: k_metric_reduce's
+// records; `what` says which of them the launch produced, the rest of a record
+// is zero.  Every record is written whole.
+__global__ __launch_bounds__(64) void k_probe_out(const uint32_t* __restrict__ heads,
+                                                  const uint32_t* __restrict__ sizes,
+                                                  const myyuv_frame_metric* __restrict__ rec, uint32_t what,
+                                                  uint32_t nframes, myyuv_probe* __restrict__ out) {
+  const uint32_t f = blockIdx.x * 64u + threadIdx.x;
+  if (f >= nframes) return;
+  myyuv_probe r = {};
+  if (what & MYYUV_PROBE_SIZE) {
+    for (int p = 0; p < 3; p++) r.plane_bytes[p] = heads[3 * f + p];
+    r.payload_bytes = sizes[f];
+  }
+  if (what & MYYUV_PROBE_METRIC) r.metric = rec[f];
+  out[f] = r;
 }
 
 }  // namespace myyuv_gpu

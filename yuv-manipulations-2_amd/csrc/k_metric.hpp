@@ -1,5 +1,6 @@
-// k_metric.hpp — what the two Compare kernels share on the device
-// (k_decode_compare, k_huff_decode.hip; k_frame_compare, k_color.hip): the
+// k_metric.hpp — what the Compare kernels share on the device
+// (k_decode_compare, k_huff_decode.hip; k_frame_compare, k_color.hip;
+// k_coef_compare, k_transform.hip): the
 // exchanges that bring a block's partial sums together, and the wave's last
 // step, one lane per block (metric.h has the arithmetic).
 #pragma once
@@ -66,6 +67,34 @@ __device__ __forceinline__ void finish(const Sums& s, bool live, uint4* part, my
     mx = max(mx, (uint32_t)__shfl_xor((int)mx, m, 64));
   }
   if (threadIdx.x % kWave == 0) *part = make_uint4(sse, (uint32_t)ss, n, mx);
+}
+
+// finish() for a wave that holds four 16-block transform units at once
+// (k_coef_compare, k_transform.hip): lane (b, q) holds block b of the wave's
+// unit q (`live`: it has one; `unit`: the wave has a unit q at all; all 64
+// lanes call this).  The totals are taken over the lanes of equal q, and lane
+// q < 4 writes unit q's slot `part` (the slot of the lane's own unit), so each
+// unit's totals stay apart: the units of a wave may lie in different planes
+// and frames.  A unit's sse total is below 2^26.
+__device__ __forceinline__ void finish_units(const Sums& s, bool live, bool unit, uint4* part,
+                                             myyuv_block_metric* entry) {
+  uint32_t sse = 0, mx = 0, n = 0;
+  int32_t ss = 0;
+  if (live) {
+    sse = myyuv_metric::sse_of(s);
+    ss = myyuv_metric::ssim_of(s);
+    mx = s.mx;
+    n = 1;
+    if (entry != nullptr) *reinterpret_cast<uint2*>(entry) = make_uint2(sse, (uint32_t)ss);
+  }
+#pragma unroll
+  for (int m = 32; m >= 4; m >>= 1) {
+    sse += (uint32_t)__shfl_xor((int)sse, m, 64);
+    ss += __shfl_xor(ss, m, 64);
+    n += (uint32_t)__shfl_xor((int)n, m, 64);
+    mx = max(mx, (uint32_t)__shfl_xor((int)mx, m, 64));
+  }
+  if (threadIdx.x % kWave < 4u && unit) *part = make_uint4(sse, (uint32_t)ss, n, mx);
 }
 
 // The slot of the wave of group (blockIdx.x) of frame (blockIdx.y) on the

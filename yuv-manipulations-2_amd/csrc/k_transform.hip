@@ -1,4 +1,5 @@
-// k_transform.hip — K1 fdct_quant and K6 dequant_idct for gfx950.
+// k_transform.hip — K1 fdct_quant and K6 dequant_idct for gfx950, and
+// k_coef_compare, K6's transform against a source frame (at the end).
 //
 // Streaming kernels: K1 reads 1 B/sample (u8 pixel) and writes 2 B/sample
 // (int16 coefficient), K6 the reverse (3 B/sample each).  The
@@ -77,6 +78,7 @@
 #include <stddef.h>
 
 #include "codec_common.hpp"
+#include "k_metric.hpp"
 #include "xform_common.hpp"
 
 // K1: 8 waves per SIMD (its LDS allows 8 workgroups per CU); the compiler
@@ -377,17 +379,21 @@ __global__ __launch_bounds__(64 * kFixWaves) void k_fdct_fix(const uint8_t* __re
   }
 }
 
-// K6: int16 coefficients (natural order, quad layout) -> u8 planes.
-// DCT.cpp:330-334 (dequant, squareMatrixMulT2, squareMatrixMul), :358-362
-// (roundf, +128, clamp).
-__global__ __launch_bounds__(256) void k_dequant_idct(const uint4* __restrict__ coef,
-                                                     const uint8_t* __restrict__ rmask,
-                                                     const uint4* __restrict__ zq, FrameGeom G,
-                                                     const QTables* __restrict__ qt,
-                                                     uint8_t* __restrict__ frame, uint4* __restrict__ sink) {
-  __shared__ float tile[4][kXfUnit * kTile];
-  __shared__ float sq[3 * 64];  // QTables::q
-  stage_tables<3 * 64>(qt->q[0], sq);
+// K6's per-wave walk over the launch's 16-block units, shared by K6 and
+// k_coef_compare: dequantise, both stages of the inverse transform in the
+// reference's order, roundf and clamp; `out` says what becomes of the pixel
+// rows.  out.begin(ua, b, q) runs once the next unit's loads are issued (a
+// place to issue loads of its own for unit ua, which then fly behind the
+// unit's arithmetic); out.rows(ua, f, U, local, q, lane, w0, w1) takes rows
+// 2q (w0) and 2q+1 (w1) of block `local` of the unit's plane in frame f;
+// out.end() runs after the wave's last unit.  tile: the workgroup's transpose
+// tiles, sq: QTables::q staged by the kernel.
+template <class Out>
+__device__ __forceinline__ void dequant_idct_units(const uint4* __restrict__ coef,
+                                                   const uint8_t* __restrict__ rmask,
+                                                   const uint4* __restrict__ zq, const FrameGeom& G,
+                                                   float (*tile)[kXfUnit * kTile], const float* sq,
+                                                   uint4* __restrict__ sink, Out& out) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t q = lane & 3u, b = lane >> 2;
   float* tb = tile[threadIdx.x >> 6] + b * kTile;
@@ -415,6 +421,7 @@ __global__ __launch_bounds__(256) void k_dequant_idct(const uint4* __restrict__ 
     load_quads(coef, zq, unit_block(G, un, b), q, nm, na, nc);  // unconditional: see K1
     un = un + stride < nall ? un + stride : un;
     nm = rmask[unit_block(G, un, b)];
+    out.begin(ua, b, q);
     wave_sync();
     // (Z[k][2q], Z[k][2q+1]) = word k*4 + q
     uint32_t zc[8];
@@ -493,19 +500,109 @@ __global__ __launch_bounds__(256) void k_dequant_idct(const uint4* __restrict__ 
                                 __builtin_amdgcn_perm(__builtin_amdgcn_perm(px[15], px[13], 0x0c0c0400u),
                                                       __builtin_amdgcn_perm(px[11], px[9], 0x0c0c0400u),
                                                       0x05040100u));
-    // ---- pixel rows 2q, 2q+1 of the block out (8 B each; lanes past the
-    // plane's end write the sink)
-    {
-      const bool live = local < U.nb;
-      const uint32_t off = block_row_offset(U, live ? local : 0u, 2u * q);
-      uint8_t* fr = frame + (size_t)f * G.fbytes;
-      uint2* d0 = live ? reinterpret_cast<uint2*>(fr + off) : reinterpret_cast<uint2*>(sink + lane);
-      uint2* d1 = live ? reinterpret_cast<uint2*>(fr + off + U.pw)
-                       : reinterpret_cast<uint2*>(sink + 64 + lane);
-      *d0 = w0;
-      *d1 = w1;
-    }
+    out.rows(ua, f, U, local, q, lane, w0, w1);
   }
+  out.end();
+}
+
+// K6's sink: pixel rows 2q, 2q+1 of the block out (8 B each; lanes past the
+// plane's end write the sink)
+struct StoreRows {
+  const FrameGeom& G;
+  uint8_t* __restrict__ frame;
+  uint4* __restrict__ sink;
+  __device__ __forceinline__ void begin(uint32_t, uint32_t, uint32_t) {}
+  __device__ __forceinline__ void rows(uint32_t, uint32_t f, const Unit& U, uint32_t local, uint32_t q, uint32_t lane,
+                                       uint2 w0, uint2 w1) {
+    const bool live = local < U.nb;
+    const uint32_t off = block_row_offset(U, live ? local : 0u, 2u * q);
+    uint8_t* fr = frame + (size_t)f * G.fbytes;
+    uint2* d0 = live ? reinterpret_cast<uint2*>(fr + off) : reinterpret_cast<uint2*>(sink + lane);
+    uint2* d1 = live ? reinterpret_cast<uint2*>(fr + off + U.pw) : reinterpret_cast<uint2*>(sink + 64 + lane);
+    *d0 = w0;
+    *d1 = w1;
+  }
+  __device__ __forceinline__ void end() {}
+};
+
+// K6: int16 coefficients (natural order, quad layout) -> u8 planes.
+// DCT.cpp:330-334 (dequant, squareMatrixMulT2, squareMatrixMul), :358-362
+// (roundf, +128, clamp).
+__global__ __launch_bounds__(256) void k_dequant_idct(const uint4* __restrict__ coef,
+                                                     const uint8_t* __restrict__ rmask,
+                                                     const uint4* __restrict__ zq, FrameGeom G,
+                                                     const QTables* __restrict__ qt,
+                                                     uint8_t* __restrict__ frame, uint4* __restrict__ sink) {
+  __shared__ float tile[4][kXfUnit * kTile];
+  __shared__ float sq[3 * 64];  // QTables::q
+  stage_tables<3 * 64>(qt->q[0], sq);
+  StoreRows out{G, frame, sink};
+  dequant_idct_units(coef, rmask, zq, G, tile, sq, sink, out);
+}
+
+// k_coef_compare: K6 with a source frame where K6 has its output (include/
+// myyuv_hip.h, "Probe").  The coefficient image is the one K1 and k_fdct_fix
+// leave (coef, rmask: K5's hand-off to K6 is the same contract), so the rows
+// are those of "compress at q, decode": where K6 stores rows 2q, 2q+1 of a
+// block, this kernel has loaded the source frame's rows from the same offsets
+// (load_rows, issued before the unit's transform, which hides the latency) and
+// adds the rows' part of the block's sums (metric.h); the block's four lanes
+// then hold its sums (mt::fold_lanes<4>).  A wave keeps four units' blocks,
+// the blocks of its unit number n in the lanes with q == n % 4, and then
+// finishes 64 blocks at once (mt::finish_units): the 24-step quotient runs
+// once per four units, every lane busy, as in k_decode_compare.  Each unit's
+// totals go to its own slot part[ua] (16 B per 16 blocks, 1/64 of the source
+// read), which k_metric_reduce adds up per plane with the planes' unit counts:
+// no atomics, every slot written by every launch.  Neither a chunk nor a
+// decoded frame exists in HBM.
+struct CompareRows {
+  const FrameGeom& G;
+  const uint8_t* __restrict__ src;
+  uint4* __restrict__ part;
+  myyuv_block_metric* __restrict__ map;
+  uint4 x = make_uint4(0, 0, 0, 0);  // the unit's source rows 2q (x, y), 2q+1 (z, w)
+  mt::Sums held;                     // the block this lane keeps
+  uint32_t held_g = 0, held_ua = 0;  // its index in the launch, its unit
+  bool held_live = false, held_unit = false;
+  uint32_t n = 0;  // units since the last finish (wave-uniform)
+  __device__ __forceinline__ void begin(uint32_t ua, uint32_t b, uint32_t q) { x = load_rows(src, G, ua, b, q); }
+  __device__ __forceinline__ void rows(uint32_t ua, uint32_t f, const Unit& U, uint32_t local, uint32_t q, uint32_t,
+                                       uint2 w0, uint2 w1) {
+    mt::Sums ps;
+    myyuv_metric::add_word(ps, x.x, w0.x);
+    myyuv_metric::add_word(ps, x.y, w0.y);
+    myyuv_metric::add_word(ps, x.z, w1.x);
+    myyuv_metric::add_word(ps, x.w, w1.y);
+    mt::fold_lanes<4>(ps);  // (the whole wave is active: the loop's branch is wave-uniform)
+    if (q == n) {
+      held = ps;
+      held_g = f * G.cum[3] + U.cum + local;
+      held_ua = ua;
+      held_live = local < U.nb;
+      held_unit = true;
+    }
+    if (++n == 4u) end();
+  }
+  __device__ __forceinline__ void end() {
+    if (n == 0u) return;  // (wave-uniform)
+    mt::finish_units(held, held_live, held_unit, part + held_ua, map != nullptr ? map + held_g : nullptr);
+    held_live = held_unit = false;
+    n = 0;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_coef_compare(const uint4* __restrict__ coef,
+                                                     const uint8_t* __restrict__ rmask,
+                                                     const uint4* __restrict__ zq, FrameGeom G,
+                                                     const QTables* __restrict__ qt,
+                                                     const uint8_t* __restrict__ src, uint4* __restrict__ part,
+                                                     myyuv_block_metric* __restrict__ map,
+                                                     uint4* __restrict__ sink) {
+  __shared__ float tile[4][kXfUnit * kTile];
+  __shared__ float sq[3 * 64];  // QTables::q
+  stage_tables<3 * 64>(qt->q[0], sq);
+  CompareRows out{G, src, part, map};
+  dequant_idct_units(coef, rmask, zq, G, tile, sq, sink, out);
 }
 
 }  // namespace myyuv_gpu

@@ -24,6 +24,7 @@
 // (after the HIP runtime header)
 #include "coef_xform.h"
 #include "fdct_bfly.h"
+#include "rate_search.h"
 
 #ifndef MYYUV_R16_BATCH
 #define MYYUV_R16_BATCH 1  // batches take the CAP-16 overflow tier too (0: single frames only)
@@ -757,6 +758,11 @@ const char* myyuv_hip_strerror(int code) {
   }
 }
 
+const char* myyuv_hip_error_message(int code) {
+  if (code == MYYUV_E_TARGET) return "target not reachable";
+  return myyuv_hip_strerror(code);
+}
+
 uint32_t myyuv_dct_payload_bound(uint32_t w, uint32_t h) {
   const uint64_t nb = (uint64_t)(w / 8) * (h / 8) + 2ull * (uint64_t)(w / 16) * (h / 16);
   const uint64_t b = 12 + 24 + nb + nb * kMaxChunk;
@@ -783,6 +789,10 @@ int myyuv_hip_create(int device, myyuv_hip_handle* out) {
         cus > 0 && n1 > 0 && n6 > 0) {
       c->xf_resident[0] = (uint32_t)(cus * n1);
       c->xf_resident[1] = (uint32_t)(cus * n6);
+      int ncc = 0;
+      c->xf_resident[2] = c->xf_resident[1];
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&ncc, k_coef_compare, 256, 0) == hipSuccess && ncc > 0)
+        c->xf_resident[2] = (uint32_t)(cus * ncc);
       int nfix = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nfix, k_fdct_fix, 64 * kFixWaves, 0) == hipSuccess &&
           nfix > 0)
@@ -1514,6 +1524,274 @@ int myyuv_gpu_dct_compare_device(myyuv_hip_handle c, const void* d_payload, cons
   return 0;
 }
 
+// ---- probe and encode to a target (defined in myyuv_hip.h) -------------------
+namespace {
+
+bool what_ok(uint32_t what) { return what >= 1 && what <= (MYYUV_PROBE_SIZE | MYYUV_PROBE_METRIC); }
+
+// The probe's scratch for a launch of nf frames: 12 head bytes per frame, the
+// payload sizes, the scan's error word (8-byte aligned).
+size_t probe_sizes_at(uint32_t nf) { return (size_t)nf * 12; }
+size_t probe_err_at(uint32_t nf) { return ((size_t)nf * 16 + 7) & ~(size_t)7; }
+
+// Workspace of a probe of G.nframes frames: the compress calls', the units'
+// totals (16 B per 16-block unit) and the plane records.
+int reserve_probe(myyuv_hip_ctx* c, const FrameGeom& G, uint32_t what) {
+  const uint32_t nf = G.nframes;
+  int e = reserve(c, G);
+  e |= c->pbsz.grow(probe_err_at(nf) + 8);
+  if (what & MYYUV_PROBE_METRIC) {
+    e |= c->mpart.grow((size_t)nf * G.ucum[3] * sizeof(uint4));
+    e |= c->mrec.grow((size_t)nf * sizeof(myyuv_frame_metric));
+  }
+  return e ? MYYUV_E_HIP : 0;
+}
+
+// One launch group of a probe: frame f at d_in + f * fbytes -> d_out[f] (and
+// its part of the map).  Size: the encoder as launch_compress runs it, up to
+// the tile scan, which is given a 12-byte "stream" per frame (it writes the
+// three plane sizes there, skips the plane headers, and reports the size; its
+// capacity overflow goes to an error word of the probe's own).  Metric: K1
+// (once, when the split encoder's size part ran it already), k_coef_compare
+// on K6's grid, k_metric_reduce over the planes' unit counts.
+int launch_probe(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_in, uint32_t what, myyuv_probe* d_out,
+                 myyuv_block_metric* d_map, hipStream_t s) {
+  const uint32_t nf = G.nframes;
+  const QTables* qt = c->qtd.as<const QTables>();
+  const uint8_t* in = static_cast<const uint8_t*>(d_in);
+  uint8_t* heads = c->pbsz.as<uint8_t>();
+  uint32_t* sizes = reinterpret_cast<uint32_t*>(heads + probe_sizes_at(nf));
+  unsigned long long* scan_err = reinterpret_cast<unsigned long long*>(heads + probe_err_at(nf));
+  int e = 0;
+  bool have_coef = false;
+  if (what & MYYUV_PROBE_SIZE) {
+    if (c->fused) {
+      uint32_t* count = c->work.as<uint32_t>();
+      e |= hipMemsetAsync(count, 0, 4, s) != hipSuccess;
+      e |= launch(c, MYYUV_K_ENCODE_TILE, k_encode_tile, dim3(G.tcum[3], nf), dim3(kK2Group), s, in, G, qt,
+                  c->coef.as<uint4>(), c->rmask.as<uint8_t>(), c->stage.as<uint32_t>(), c->tinfo.as<uint32_t>(),
+                  c->sizes.as<uint8_t>(), c->srcoff.as<uint32_t>(), count + 64, count);
+      e |= launch_overflow(c, G, s);
+    } else {
+      e |= launch_fdct(c, G, in, qt, c->work.as<uint32_t>(), s);
+      if ((c->skip >> MYYUV_K_FDCT) & 1u) e |= hipMemsetAsync(c->work.p, 0, 4, s) != hipSuccess;  // (see launch_compress)
+      e |= launch_huff_encode(c, G, s);
+      have_coef = true;
+    }
+    e |= launch(c, MYYUV_K_SCAN, k_tile_scan, dim3(nf), dim3(256), s, c->tinfo.as<uint32_t>(), G, heads, 12u, sizes,
+                scan_err);
+  }
+  if (what & MYYUV_PROBE_METRIC) {
+    if (!have_coef) e |= launch_fdct(c, G, in, qt, nullptr, s);
+    e |= launch(c, MYYUV_K_COEF_CMP, k_coef_compare, xf_grid(G, c->xf_resident[2]), dim3(256), s,
+                c->coef.as<const uint4>(), c->rmask.as<const uint8_t>(), c->zq.as<const uint4>(), G, qt, in,
+                c->mpart.as<uint4>(), d_map, c->sink.as<uint4>());
+    e |= launch(c, MYYUV_K_METRIC_SUM, k_metric_reduce, dim3(3, nf), dim3(256), s, c->mpart.as<const uint4>(),
+                G.ucum[1] - G.ucum[0], G.ucum[2] - G.ucum[1], G.ucum[3] - G.ucum[2], c->mrec.as<myyuv_frame_metric>());
+  }
+  e |= launch(c, MYYUV_K_PROBE_OUT, k_probe_out, dim3(ceil_div(nf, 64)), dim3(64), s,
+              reinterpret_cast<const uint32_t*>(heads), (const uint32_t*)sizes,
+              c->mrec.as<const myyuv_frame_metric>(), what, nf, d_out);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+// One frame on the device at quality q: the record read back (the search's
+// step; synchronous).  Workspace: reserve_probe, c->prec.
+int probe_once(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_frame, const uint8_t q[3], uint32_t what,
+               myyuv_block_metric* d_map, hipStream_t s, myyuv_probe* out) {
+  int e;
+  if ((e = set_qtables(c, q, s)) || (e = launch_probe(c, G, d_frame, what, c->prec.as<myyuv_probe>(), d_map, s)))
+    return e;
+  return d2h(out, c->prec.p, sizeof(*out), s);
+}
+
+// The search over probes of the frame at d_frame, then (unless the target is
+// out of reach) the ordinary compress at the chosen qualities into d_payload.
+// Synchronous up to the compress launch.
+int target_search(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_frame, myyuv_rate::Search& S, void* d_payload,
+                  uint32_t cap, uint32_t* d_size, myyuv_target_result* result, hipStream_t s) {
+  int e;
+  if ((e = reserve_probe(c, G, MYYUV_PROBE_SIZE | MYYUV_PROBE_METRIC)) || c->prec.grow(sizeof(myyuv_probe)))
+    return e ? e : MYYUV_E_HIP;
+  // What the search's probes said, by quality: the sizes of (q, q, q) in size
+  // mode, plane p's record at its quality q in distortion mode (a plane's
+  // figures depend on its own quality alone).  The result's qualities were
+  // all probed (each is 1, 100, or a mid that became lo or hi), so `at` takes
+  // that part from here and the other part from one launch after the search.
+  std::vector<myyuv_probe> seen(101);
+  uint8_t q[3];
+  myyuv_probe pr;
+  while (S.next(q)) {
+    if ((e = probe_once(c, G, d_frame, q, S.size_mode ? MYYUV_PROBE_SIZE : MYYUV_PROBE_METRIC, nullptr, s, &pr)))
+      return e;
+    const uint64_t sse[3] = {pr.metric.plane[0].sse, pr.metric.plane[1].sse, pr.metric.plane[2].sse};
+    if (S.size_mode) {
+      std::memcpy(seen[q[0]].plane_bytes, pr.plane_bytes, sizeof(pr.plane_bytes));
+      seen[q[0]].payload_bytes = pr.payload_bytes;
+    } else {
+      for (int p = 0; p < 3; p++) seen[q[p]].metric.plane[p] = pr.metric.plane[p];
+    }
+    S.answer(pr.payload_bytes, sse);
+  }
+  std::memcpy(result->quality, S.quality, 3);
+  result->failed_planes = S.failed_planes;
+  result->probes = S.probes;
+  if ((e = probe_once(c, G, d_frame, S.quality, S.size_mode ? MYYUV_PROBE_METRIC : MYYUV_PROBE_SIZE, nullptr, s,
+                      &result->at)))
+    return e;
+  if (S.size_mode) {
+    std::memcpy(result->at.plane_bytes, seen[S.quality[0]].plane_bytes, sizeof(pr.plane_bytes));
+    result->at.payload_bytes = seen[S.quality[0]].payload_bytes;
+  } else {
+    for (int p = 0; p < 3; p++) result->at.metric.plane[p] = seen[S.quality[p]].metric.plane[p];
+  }
+  if (S.failed) return MYYUV_E_TARGET;
+  if ((e = set_qtables(c, S.quality, s))) return e;
+  return launch_compress(c, G, d_frame, d_payload, cap, d_size, s);
+}
+
+int target_host(myyuv_hip_ctx* c, const uint8_t* iyuv, uint32_t w, uint32_t h, myyuv_rate::Search& S,
+                uint8_t* payload, uint32_t cap, uint32_t* payload_size, myyuv_target_result* result) {
+  if (result) std::memset(result, 0, sizeof(*result));
+  if (!c || !iyuv || !payload || !payload_size || !result) return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = make_geom(w, h, G);
+  if (e) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const uint32_t bound = myyuv_dct_payload_bound(w, h);
+  if (c->frame.grow(G.fbytes) || c->payload.grow(bound)) return MYYUV_E_HIP;
+  if (reset_err(c, s) || h2d(c->frame.p, iyuv, G.fbytes, s)) return MYYUV_E_HIP;
+  e = target_search(c, G, c->frame.p, S, c->payload.p, bound, c->psize.as<uint32_t>(), result, s);
+  if (e) {
+    if (c->prof) drain_profile(c);
+    return e;
+  }
+  uint32_t size = 0;
+  if (d2h(&size, c->psize.p, 4, s)) return MYYUV_E_HIP;
+  if ((e = read_err(c, s, nullptr))) {
+    (void)reset_err(c, s);
+    return e;
+  }
+  *payload_size = size;
+  if (size > cap) return MYYUV_E_CAPACITY;
+  if (d2h(payload, c->payload.p, size, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+int target_device(myyuv_hip_ctx* c, const void* d_iyuv, uint32_t w, uint32_t h, myyuv_rate::Search& S,
+                  void* d_payload, uint32_t cap, uint32_t* d_payload_size, myyuv_target_result* result,
+                  void* stream) {
+  if (result) std::memset(result, 0, sizeof(*result));
+  if (!c || !d_iyuv || !d_payload || !d_payload_size || !result) return MYYUV_E_ARG;
+  if (((uintptr_t)d_payload & 3) || ((uintptr_t)d_iyuv & 7)) return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = make_geom(w, h, G);
+  if (e) return e;
+  Entry en(c, stream);
+  if ((e = target_search(c, G, d_iyuv, S, d_payload, cap, d_payload_size, result, en.s))) return e;
+  if (hipStreamSynchronize(en.s) != hipSuccess) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+}  // namespace
+
+uint64_t myyuv_metric_sse_for_psnr(double db, uint64_t nsamples) {
+  return myyuv_rate::sse_for_psnr(db, nsamples, myyuv_metric_psnr);
+}
+
+int myyuv_gpu_dct_probe(myyuv_hip_handle c, const uint8_t* iyuv, uint32_t w, uint32_t h, const uint8_t q[3],
+                        uint32_t what, myyuv_probe* out, myyuv_block_metric* map) {
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!c || !iyuv || !out || !q) return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = check_q(q);
+  if (e || (e = make_geom(w, h, G))) return e;
+  if (!what_ok(what)) return MYYUV_E_ARG;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const bool with_map = map && (what & MYYUV_PROBE_METRIC);
+  if ((e = reserve_probe(c, G, what))) return e;
+  if (c->frame.grow(G.fbytes) || c->prec.grow(sizeof(myyuv_probe)) ||
+      (with_map && c->mmap.grow((size_t)G.cum[3] * sizeof(myyuv_block_metric))))
+    return MYYUV_E_HIP;
+  if (h2d(c->frame.p, iyuv, G.fbytes, s)) return MYYUV_E_HIP;
+  myyuv_probe r;
+  if ((e = set_qtables(c, q, s)) ||
+      (e = launch_probe(c, G, c->frame.p, what, c->prec.as<myyuv_probe>(),
+                        with_map ? c->mmap.as<myyuv_block_metric>() : nullptr, s)))
+    return e;
+  if (with_map && hipMemcpyAsync(map, c->mmap.p, (size_t)G.cum[3] * sizeof(myyuv_block_metric),
+                                 hipMemcpyDeviceToHost, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  if (d2h(&r, c->prec.p, sizeof(r), s)) return MYYUV_E_HIP;
+  *out = r;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+int myyuv_gpu_dct_probe_device(myyuv_hip_handle c, const void* d_iyuv, uint32_t nframes, uint32_t w, uint32_t h,
+                               const uint8_t q[3], uint32_t what, myyuv_probe* d_out, myyuv_block_metric* d_map,
+                               void* stream) {
+  if (!c || !d_iyuv || !d_out || !q) return MYYUV_E_ARG;
+  if (((uintptr_t)d_iyuv & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_map & 7)) return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = check_q(q);
+  if (e || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes))) return e;
+  if (!what_ok(what)) return MYYUV_E_ARG;
+  Entry en(c, stream);
+  // (as several launches when the batch's coefficient image would reach 4 GiB; k_metric_reduce's grid: 65,535 frames)
+  const uint32_t per = std::min(launch_frames(G, c->launch_blocks), 65535u);
+  FrameGeom GL = G;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve_probe(c, GL, what)) ||
+      (e = set_qtables(c, q, en.s)))
+    return e;
+  if (!(what & MYYUV_PROBE_METRIC)) d_map = nullptr;
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GL.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
+    const uint8_t* fr = static_cast<const uint8_t*>(d_iyuv) + (size_t)f0 * G.fbytes;
+    if ((e = launch_probe(c, GL, fr, what, d_out + f0, d_map ? d_map + (size_t)f0 * G.cum[3] : nullptr, en.s)))
+      return e;
+  }
+  return 0;
+}
+
+int myyuv_gpu_dct_compress_to_size(myyuv_hip_handle c, const uint8_t* iyuv, uint32_t w, uint32_t h,
+                                   uint32_t max_payload_bytes, uint8_t* payload, uint32_t cap,
+                                   uint32_t* payload_size, myyuv_target_result* result) {
+  myyuv_rate::Search S = myyuv_rate::Search::size(max_payload_bytes);
+  return target_host(c, iyuv, w, h, S, payload, cap, payload_size, result);
+}
+
+int myyuv_gpu_dct_compress_to_sse(myyuv_hip_handle c, const uint8_t* iyuv, uint32_t w, uint32_t h,
+                                  const uint64_t max_sse[3], uint8_t* payload, uint32_t cap, uint32_t* payload_size,
+                                  myyuv_target_result* result) {
+  if (result) std::memset(result, 0, sizeof(*result));
+  if (!max_sse) return MYYUV_E_ARG;
+  myyuv_rate::Search S = myyuv_rate::Search::sse(max_sse);
+  return target_host(c, iyuv, w, h, S, payload, cap, payload_size, result);
+}
+
+int myyuv_gpu_dct_compress_to_size_device(myyuv_hip_handle c, const void* d_iyuv, uint32_t w, uint32_t h,
+                                          uint32_t max_payload_bytes, void* d_payload, uint32_t cap,
+                                          uint32_t* d_payload_size, myyuv_target_result* result, void* stream) {
+  myyuv_rate::Search S = myyuv_rate::Search::size(max_payload_bytes);
+  return target_device(c, d_iyuv, w, h, S, d_payload, cap, d_payload_size, result, stream);
+}
+
+int myyuv_gpu_dct_compress_to_sse_device(myyuv_hip_handle c, const void* d_iyuv, uint32_t w, uint32_t h,
+                                         const uint64_t max_sse[3], void* d_payload, uint32_t cap,
+                                         uint32_t* d_payload_size, myyuv_target_result* result, void* stream) {
+  if (result) std::memset(result, 0, sizeof(*result));
+  if (!max_sse) return MYYUV_E_ARG;
+  myyuv_rate::Search S = myyuv_rate::Search::sse(max_sse);
+  return target_device(c, d_iyuv, w, h, S, d_payload, cap, d_payload_size, result, stream);
+}
+
 // ---- requantise and transform (defined in myyuv_hip.h) ----------------------
 namespace {
 
@@ -2170,7 +2448,7 @@ int myyuv_gpu_dct_decompress_to_bmp_frames(myyuv_hip_handle c, const uint8_t* co
 }
 
 int myyuv_hip_profile(myyuv_hip_handle c, int enable) {
-  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_END) - 1u : 0u);
+  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_LIMIT) - 1u : 0u);
 }
 
 int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
@@ -2179,8 +2457,8 @@ int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
   DeviceGuard g(c->device);
   (void)hipStreamSynchronize(c->stream);
   drain_profile(c);
-  c->prof = mask & ((1u << MYYUV_K_END) - 1u);
-  for (int k = 0; k < MYYUV_K_END; k++) {
+  c->prof = mask & ((1u << MYYUV_K_LIMIT) - 1u);
+  for (int k = 0; k < MYYUV_K_LIMIT; k++) {
     c->ms[k] = 0;
     c->launches[k] = 0;
   }
@@ -2193,8 +2471,8 @@ int myyuv_hip_kernel_stats_n(myyuv_hip_handle c, uint32_t n, double* ms, int64_t
   DeviceGuard g(c->device);
   drain_profile(c);
   for (uint32_t k = 0; k < n; k++) {
-    ms[k] = k < MYYUV_K_END ? c->ms[k] : 0.0;
-    launches[k] = k < MYYUV_K_END ? c->launches[k] : 0;
+    ms[k] = k < MYYUV_K_LIMIT ? c->ms[k] : 0.0;
+    launches[k] = k < MYYUV_K_LIMIT ? c->launches[k] : 0;
   }
   return 0;
 }

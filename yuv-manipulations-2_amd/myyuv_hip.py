@@ -28,15 +28,21 @@ KERNELS = ["fdct_quant", "huff_encode", "scan_tiles", "stream_out", "encode_tile
  K_HUFF_R16, K_HUFF_WAVE, K_BMP, K_FDCT_FIX, K_IYUV_BMP, K_REGION, K_SCALED, K_REQUANT,
  K_COEF_XF) = range(len(KERNELS))
 # KERNELS is the fixed-length list of myyuv_hip_kernel_stats (MYYUV_K_COUNT: part of that call's
-# ABI, it does not grow); ids from there on are read with myyuv_hip_kernel_stats_n, and
-# Codec.profile / Codec.kernel_stats take and return the names of KERNELS_ALL
+# ABI, it does not grow); ids from there on are read with myyuv_hip_kernel_stats_n
 KERNELS_ALL = KERNELS + ["stream_gather", "decode_compare", "frame_compare", "metric_reduce"]
 K_GATHER = KERNELS_ALL.index("stream_gather")
 K_TOTAL = K_GATHER + 1  # MYYUV_K_TOTAL: frozen like MYYUV_K_COUNT; the ids after it end at K_END
 K_COMPARE = KERNELS_ALL.index("decode_compare")
 K_FRAME_CMP = KERNELS_ALL.index("frame_compare")
 K_METRIC_SUM = KERNELS_ALL.index("metric_reduce")
-K_END = len(KERNELS_ALL)  # MYYUV_K_END
+K_END = len(KERNELS_ALL)  # MYYUV_K_END: frozen like the two bounds before it; the ids after it end at K_LIMIT
+# every kernel: Codec.profile / Codec.kernel_stats take and return these names (KERNELS_ALL's and the probe's)
+KERNELS_EVERY = KERNELS_ALL + ["coef_compare", "probe_out"]
+K_COEF_CMP = KERNELS_EVERY.index("coef_compare")
+K_PROBE_OUT = KERNELS_EVERY.index("probe_out")
+K_LIMIT = len(KERNELS_EVERY)  # MYYUV_K_LIMIT
+E_TARGET = 18  # MYYUV_E_TARGET: "target not reachable" (error_message; strerror's table ends at 17)
+PROBE_SIZE, PROBE_METRIC = 1, 2  # MYYUV_PROBE_*
 # myyuv_block_metric, as the maps of the compare calls come back
 BLOCK_METRIC = np.dtype([("sse", np.uint32), ("ssim", np.int32)])
 SSIM_ONE = 1 << 24  # ssim of identical blocks
@@ -71,6 +77,9 @@ EXPORTS = [
     "myyuv_gpu_dct_crop", "myyuv_gpu_dct_crop_device", "myyuv_gpu_dct_join", "myyuv_gpu_dct_join_device",
     "myyuv_metric_psnr", "myyuv_metric_ssim", "myyuv_gpu_iyuv_compare", "myyuv_gpu_iyuv_compare_device",
     "myyuv_gpu_dct_compare", "myyuv_gpu_dct_compare_device",
+    "myyuv_gpu_dct_probe", "myyuv_gpu_dct_probe_device", "myyuv_metric_sse_for_psnr", "myyuv_hip_error_message",
+    "myyuv_gpu_dct_compress_to_size", "myyuv_gpu_dct_compress_to_sse",
+    "myyuv_gpu_dct_compress_to_size_device", "myyuv_gpu_dct_compress_to_sse_device",
 ]
 
 
@@ -88,6 +97,31 @@ class FrameMetric(ctypes.Structure):
         """((sse, ssim_sum, nblocks, max_abs) of Y, of U, of V), plain ints."""
         return tuple((int(p.sse), int(p.ssim_sum), int(p.nblocks), int(p.max_abs)) for p in self.plane)
 
+
+class Probe(ctypes.Structure):
+    """myyuv_probe (88 B)"""
+    _fields_ = [("plane_bytes", ctypes.c_uint32 * 3), ("payload_bytes", ctypes.c_uint32), ("metric", FrameMetric)]
+
+    def as_ints(self):
+        """((plane bytes of Y, U, V), payload bytes, FrameMetric.as_ints()), plain ints."""
+        return (tuple(int(v) for v in self.plane_bytes), int(self.payload_bytes), self.metric.as_ints())
+
+
+class TargetResult(ctypes.Structure):
+    """myyuv_target_result"""
+    _fields_ = [("quality", ctypes.c_uint8 * 3), ("failed_planes", ctypes.c_uint8), ("probes", ctypes.c_uint32),
+                ("at", Probe)]
+
+    def as_dict(self):
+        return {"quality": tuple(int(v) for v in self.quality), "failed_planes": int(self.failed_planes),
+                "probes": int(self.probes), "at": self.at.as_ints()}
+
+
+# myyuv_probe as an array's element (probe_device's d_out read back)
+PROBE_DTYPE = np.dtype([("plane_bytes", np.uint32, 3), ("payload_bytes", np.uint32),
+                        ("metric", [("sse", np.uint64), ("ssim_sum", np.int64), ("nblocks", np.uint32),
+                                    ("max_abs", np.uint32)], 3)])
+
 _lib = None
 # myyuv_payload_alloc_fn
 PAYLOAD_ALLOC = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32)
@@ -99,7 +133,8 @@ class CodecError(RuntimeError):
     def __init__(self, code, bad_block=-1):
         self.code = code
         self.bad_block = bad_block
-        super().__init__(strerror(code) if _lib is not None else f"error {code}")
+        self.result = None  # E_TARGET: TargetResult.as_dict() of the failing probe
+        super().__init__(error_message(code) if _lib is not None else f"error {code}")
 
 
 def _share_hip_runtime_with_torch():
@@ -133,6 +168,8 @@ def load():
     L.myyuv_hip_destroy.restype = None
     L.myyuv_hip_strerror.argtypes = [ctypes.c_int]
     L.myyuv_hip_strerror.restype = ctypes.c_char_p
+    L.myyuv_hip_error_message.argtypes = [ctypes.c_int]
+    L.myyuv_hip_error_message.restype = ctypes.c_char_p
     L.myyuv_dct_payload_bound.argtypes = [u32, u32]
     L.myyuv_dct_payload_bound.restype = u32
     L.myyuv_gpu_dct_compress.argtypes = [vp, u8p, u32, u32, u8p, u8p, u32, ctypes.POINTER(u32)]
@@ -198,6 +235,16 @@ def load():
     L.myyuv_gpu_iyuv_compare_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]
     L.myyuv_gpu_dct_compare.argtypes = [vp, u8p, u32, u32, u32, u8p, u8p, fmp, vp, i64p]
     L.myyuv_gpu_dct_compare_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, vp, u32, vp, vp, vp]
+    prp, trp = ctypes.POINTER(Probe), ctypes.POINTER(TargetResult)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.myyuv_gpu_dct_probe.argtypes = [vp, u8p, u32, u32, u8p, u32, prp, vp]
+    L.myyuv_gpu_dct_probe_device.argtypes = [vp, vp, u32, u32, u32, u8p, u32, vp, vp, vp]
+    L.myyuv_metric_sse_for_psnr.argtypes = [ctypes.c_double, ctypes.c_uint64]
+    L.myyuv_metric_sse_for_psnr.restype = ctypes.c_uint64
+    L.myyuv_gpu_dct_compress_to_size.argtypes = [vp, u8p, u32, u32, u32, u8p, u32, ctypes.POINTER(u32), trp]
+    L.myyuv_gpu_dct_compress_to_sse.argtypes = [vp, u8p, u32, u32, u64p, u8p, u32, ctypes.POINTER(u32), trp]
+    L.myyuv_gpu_dct_compress_to_size_device.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, trp, vp]
+    L.myyuv_gpu_dct_compress_to_sse_device.argtypes = [vp, vp, u32, u32, u64p, vp, u32, vp, trp, vp]
     L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -212,6 +259,11 @@ def strerror(code):
     return load().myyuv_hip_strerror(int(code)).decode()
 
 
+def error_message(code):
+    """myyuv_hip_error_message: the text of every code (strerror's for the codes up to 17)."""
+    return load().myyuv_hip_error_message(int(code)).decode()
+
+
 def payload_bound(w, h):
     return load().myyuv_dct_payload_bound(w, h)
 
@@ -224,6 +276,11 @@ def metric_psnr(sse, nsamples):
 def metric_ssim(ssim_sum, nblocks):
     """myyuv_metric_ssim: ssim_sum / (nblocks * 2^24)."""
     return load().myyuv_metric_ssim(int(ssim_sum), int(nblocks))
+
+
+def metric_sse_for_psnr(db, nsamples):
+    """myyuv_metric_sse_for_psnr: the largest sse whose PSNR over nsamples is at least db."""
+    return int(load().myyuv_metric_sse_for_psnr(float(db), int(nsamples)))
 
 
 def k2_constants():
@@ -644,6 +701,89 @@ class Codec:
         if rc:
             raise CodecError(rc)
 
+    # -- probe and encode to a target (defined in include/myyuv_hip.h) --
+    def probe(self, iyuv, w, h, q, what=PROBE_SIZE | PROBE_METRIC, want_map=False):
+        """What quality q would cost and give, no stream written:
+        Probe.as_ints() = ((plane bytes), payload bytes, the frame metric);
+        the part `what` leaves out is zero.  With want_map also the per-block
+        map of the metric part (a BLOCK_METRIC array)."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(iyuv).cast("B"), np.uint8))
+        if src.size < int(w) * int(h) * 3 // 2:
+            raise ValueError("frame smaller than W*H*3/2")
+        out = Probe()
+        bmap = np.zeros(max(1, (w // 8) * (h // 8) + 2 * (w // 16) * (h // 16)), BLOCK_METRIC) if want_map else None
+        rc = load().myyuv_gpu_dct_probe(self._h, _u8(src), w, h, _u8(_q(q)), int(what), ctypes.byref(out),
+                                        bmap.ctypes.data if want_map else None)
+        if rc:
+            raise CodecError(rc)
+        return (out.as_ints(), bmap) if want_map else out.as_ints()
+
+    def probe_device(self, d_iyuv, nframes, w, h, q, what, d_out, d_map=None, stream=None):
+        """Device-resident batch of probe: frame f -> d_out[f] (myyuv_probe,
+        88 B, PROBE_DTYPE) and the map at d_map when given; asynchronous."""
+        rc = load().myyuv_gpu_dct_probe_device(self._h, d_iyuv, nframes, w, h, _u8(_q(q)), int(what), d_out, d_map,
+                                               stream)
+        if rc:
+            raise CodecError(rc)
+
+    def _target(self, call, iyuv, w, h, target):
+        src = np.ascontiguousarray(np.frombuffer(memoryview(iyuv).cast("B"), np.uint8))
+        if src.size < int(w) * int(h) * 3 // 2:
+            raise ValueError("frame smaller than W*H*3/2")
+        cap = payload_bound(w, h)
+        out = np.empty(cap, np.uint8)
+        size = ctypes.c_uint32(0)
+        res = TargetResult()
+        rc = call(self._h, _u8(src), w, h, target, _u8(out), cap, ctypes.byref(size), ctypes.byref(res))
+        if rc:
+            e = CodecError(rc)
+            e.result = res.as_dict()
+            raise e
+        return out[: size.value].tobytes(), res.as_dict()
+
+    def compress_to_size(self, iyuv, w, h, max_payload_bytes):
+        """The payload of the quality the size bisection (include/myyuv_hip.h)
+        finds for a budget of max_payload_bytes, and the result as a dict
+        (quality, failed_planes, probes, at).  E_TARGET: CodecError with
+        .result the failing probe."""
+        return self._target(load().myyuv_gpu_dct_compress_to_size, iyuv, w, h, int(max_payload_bytes))
+
+    def compress_to_sse(self, iyuv, w, h, max_sse):
+        """As compress_to_size, for a squared-error ceiling per plane."""
+        t = (ctypes.c_uint64 * 3)(*(int(v) for v in max_sse))
+        return self._target(load().myyuv_gpu_dct_compress_to_sse, iyuv, w, h, t)
+
+    def compress_to_psnr(self, iyuv, w, h, db):
+        """As compress_to_sse, every plane's PSNR at least db (a number, or one per plane)."""
+        dbs = [float(v) for v in (db if isinstance(db, (tuple, list)) else (db, db, db))]
+        if any(v != v for v in dbs):
+            raise CodecError(E_ARG)
+        n = (int(w) * int(h), int(w) * int(h) // 4, int(w) * int(h) // 4)
+        return self.compress_to_sse(iyuv, w, h, [metric_sse_for_psnr(dbs[p], n[p]) for p in range(3)])
+
+    def compress_to_size_device(self, d_iyuv, w, h, max_payload_bytes, d_payload, cap, d_size, stream=None):
+        """Device-resident compress_to_size; blocks until the payload is
+        written (the search reads each probe back).  Returns the result dict."""
+        res = TargetResult()
+        rc = load().myyuv_gpu_dct_compress_to_size_device(self._h, d_iyuv, w, h, int(max_payload_bytes), d_payload,
+                                                          cap, d_size, ctypes.byref(res), stream)
+        if rc:
+            e = CodecError(rc)
+            e.result = res.as_dict()
+            raise e
+        return res.as_dict()
+
+    def compress_to_sse_device(self, d_iyuv, w, h, max_sse, d_payload, cap, d_size, stream=None):
+        res = TargetResult()
+        t = (ctypes.c_uint64 * 3)(*(int(v) for v in max_sse))
+        rc = load().myyuv_gpu_dct_compress_to_sse_device(self._h, d_iyuv, w, h, t, d_payload, cap, d_size,
+                                                         ctypes.byref(res), stream)
+        if rc:
+            e = CodecError(rc)
+            e.result = res.as_dict()
+            raise e
+        return res.as_dict()
+
     # -- requantise: a DCT stream re-encoded at another quality on its coefficients,
     # no pixels in between (defined in include/myyuv_hip.h) --
     def requantize(self, payload, w, h, q_src, q_dst):
@@ -830,19 +970,19 @@ class Codec:
         if kernels is None:
             rc = load().myyuv_hip_profile(self._h, 1 if enable else 0)
         else:
-            mask = sum(1 << KERNELS_ALL.index(k) for k in kernels) if enable else 0
+            mask = sum(1 << KERNELS_EVERY.index(k) for k in kernels) if enable else 0
             rc = load().myyuv_hip_profile_kernels(self._h, mask)
         if rc:
             raise CodecError(rc)
 
     def kernel_stats(self):
-        """{name: (summed ms, launches)} for every name of KERNELS_ALL."""
-        ms = (ctypes.c_double * K_END)()
-        n = (ctypes.c_int64 * K_END)()
-        rc = load().myyuv_hip_kernel_stats_n(self._h, K_END, ms, n)
+        """{name: (summed ms, launches)} for every name of KERNELS_EVERY."""
+        ms = (ctypes.c_double * K_LIMIT)()
+        n = (ctypes.c_int64 * K_LIMIT)()
+        rc = load().myyuv_hip_kernel_stats_n(self._h, K_LIMIT, ms, n)
         if rc:
             raise CodecError(rc)
-        return {KERNELS_ALL[i]: (ms[i], n[i]) for i in range(K_END)}
+        return {KERNELS_EVERY[i]: (ms[i], n[i]) for i in range(K_LIMIT)}
 
     def tinfo_guard(self, ntiles, arm):
         """Diagnostic (not in include/myyuv_hip.h): arm=True writes a canary
