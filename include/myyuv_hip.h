@@ -62,7 +62,24 @@ typedef struct myyuv_hip_ctx* myyuv_hip_handle;
  * its workspace, so they run in call order even on different streams: a call
  * on a stream other than the previous call's makes its stream wait for the
  * previous call's work (an event recorded at the end of every call).  For
- * concurrency, use one context per stream. */
+ * concurrency, use one context per stream.
+ *
+ * Kernel arrangements, read from the environment when the context is created
+ * (every arrangement gives the same bytes, codes and block indices):
+ *   MYYUV_ENCODER  split (default): K1 -> K2 through HBM; fused: one pass.
+ *   MYYUV_DECODER  fused (default): K5 + K6 in one kernel, the coefficients
+ *                  kept on chip.  A launch of at least MYYUV_DEC_SPAN_MIN
+ *                  64-block groups (frames x groups per frame) runs a wave per
+ *                  256-block span, which finishes one-symbol chunks in closed
+ *                  form and decodes the rest in passes of 64; a smaller one
+ *                  (a single frame has too few spans to fill the device) a
+ *                  wave per 64-block group.
+ *                  span / group: always the one / the other.
+ *                  split: K5 -> K6 through HBM.
+ *   MYYUV_DEC_SPAN_MIN  the threshold above, in groups; its default is the
+ *                  measured crossover.
+ * Region, scaled, requantise, transform and compare decode are the same
+ * kernels under every MYYUV_DECODER. */
 int myyuv_hip_create(int device, myyuv_hip_handle* out);
 void myyuv_hip_destroy(myyuv_hip_handle h);
 const char* myyuv_hip_strerror(int code);

@@ -313,6 +313,32 @@ __host__ __device__ __forceinline__ void single_chunk_words(uint32_t so, uint32_
   w0 = 0x00030001u;
   w1 = so & 0x7FFu;
 }
+// The inverse, for a decoder: whether a 7-byte chunk is single_chunk_words of
+// some key, bit for bit (h = its bytes 0..3, t = its bytes 3..6, both
+// little-endian: two 4-byte reads that stay inside the chunk), and the key.
+// Anything else of 7 bytes (a one-symbol message of several positions, junk
+// in the value's five padding bits or in the code byte, a malformed header)
+// is not, and is decoded like any other chunk.
+__host__ __device__ __forceinline__ bool single_chunk_key(uint32_t h, uint32_t t, uint32_t& key) {
+  key = (t >> 8) & 0x7FFu;
+  return h == 0x00030001u && (t & 0xFFF800FFu) == 0u;
+}
+// Blocks per wave of the span decoder (k_decode_span): 2, 4 or 8 of the
+// 64-block groups whose starts k_scan_chain keeps.
+#ifndef MYYUV_DEC_SPAN
+#define MYYUV_DEC_SPAN 256
+#endif
+constexpr uint32_t kDecSpan = MYYUV_DEC_SPAN;
+static_assert(kDecSpan == 128 || kDecSpan == 256 || kDecSpan == 512, "kDecSpan: 128, 256 or 512");
+// The fused decoder takes spans from this many 64-block groups per launch on
+// (MYYUV_DEC_SPAN_MIN overrides it).  A span wave's fixed latency is about
+// twice a group wave's (a single 4032x3008 frame, 4,443 groups: 58 against
+// 26 us) and its cost per frame 12 % lower, so alone the two kernels cross at
+// about 100k groups, but in flight with other launch groups the 24-frame 4K
+// batches (72.9k groups) already gain 1.4-2.1 % and 32 4032x3008 frames
+// (142k) 4.4 %; single frames (up to 8192^2: 24.6k groups) stay on the group
+// kernel (profiles/r9a_span_ab.txt)
+constexpr uint32_t kDecSpanMinDefault = 65536;
 // The hand-off is laid out for exactly four K2 waves per tile: k_tile_scan sums
 // tinfo words 1..4, k_stream_out keeps four run totals, k_encode_tile's
 // phase 1 covers 4 waves x 4 units x 16 blocks, and tinfo word kTInfoPrefix

@@ -30,6 +30,9 @@ __global__ void k_dequant_idct(const uint4*, const uint8_t*, const uint4*, Frame
 __global__ void k_decode_idct(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
                               const uint32_t*, FrameGeom, uint32_t, uint32_t, const QTables*, uint4*, uint8_t*,
                               unsigned long long*);
+__global__ void k_decode_span(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
+                              const uint32_t*, FrameGeom, uint32_t, uint32_t, const QTables*, uint4*, uint8_t*,
+                              unsigned long long*);
 __global__ void k_decode_region(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
                                 const uint32_t*, FrameGeom, FrameGeom, RegionSegs, const QTables*, uint8_t*,
                                 unsigned long long*);
@@ -189,9 +192,13 @@ struct myyuv_hip_ctx {
   // encoder: K1 -> K2 through HBM (split), or the fused single-pass kernel
   // k_encode_tile (MYYUV_ENCODER=fused|split)
   bool fused = false;
-  // decoder: the fused k_decode_idct (default), or K5 -> K6 through HBM
-  // (MYYUV_DECODER=split)
+  // decoder: fused (default), or K5 -> K6 through HBM (MYYUV_DECODER=split).
+  // The fused decoder is k_decode_span (a wave per kDecSpan-block span) for
+  // launches of at least dec_span_min 64-block groups (MYYUV_DEC_SPAN_MIN) and
+  // k_decode_idct (a wave per group) below: a small launch has too few spans
+  // to fill the chip.  MYYUV_DECODER=span / group: always the one / the other.
   bool fused_dec = true;
+  uint32_t dec_span_min = kDecSpanMinDefault;
   // chained scan (k_chain.hpp): per-tile status words tagged with the launch
   // epoch, counted here
   DevBuf status;

@@ -222,6 +222,9 @@ __device__ __forceinline__ int parse_table(const Chunk& c, uint32_t s, Table& T,
 // read by one position, measured no faster on MI355X, and with the loads
 // three positions ahead the decoded values came out wrong nondeterministically
 // in long straight-line groups: both are deliberately not done.)
+// (ZeroBit: the stage bit of the wave's zero quad; the span decoder's stage
+// is shorter)
+template <uint32_t ZeroBit = kZeroBit>
 __device__ __forceinline__ bool decode_regular(const LdsChunk& c, const Table& T, const uint32_t* gcol, bool act,
                                                uint32_t (&nw)[32]) {
   bool bad = false;
@@ -258,7 +261,7 @@ __device__ __forceinline__ bool decode_regular(const LdsChunk& c, const Table& T
 #else
     const uint32_t vbit = ((uint32_t)(rwin >> 32) >> ((31u - n) & 31u)) * 11u + G;
 #endif
-    const uint32_t P = take ? vbit : kZeroBit, w = P >> 5;  // (stage bits; kZeroBit: the zero quad)
+    const uint32_t P = take ? vbit : ZeroBit, w = P >> 5;  // (stage bits; ZeroBit: the zero quad)
     const uint32_t raw = funnel(c.st[w + 1], c.st[w], P);
     const uint32_t v = (uint32_t)(((int32_t)(raw << 21)) >> 21);
     const int z = c_zz[j];
@@ -604,6 +607,24 @@ __global__ __launch_bounds__(64, MYYUV_K5S_WAVES) void k_huff_decode(const uint8
   }
 }
 
+// The pixel of a block whose only nonzero coefficient may be the DC, four
+// times in a word (k_decode_idct's comment on such blocks derives it): with
+// Z[0][0] = z, R = fl(fl(c * z) * c) for all 64 pixels, c the one value of the
+// literal basis' row 0 — the full transform's two roundings, then its clamp
+// and rounding to a pixel.  q0 = Q[0][0] of the plane.
+__device__ __forceinline__ uint32_t dc_block_pixels(int16_t dc, float q0) {
+  constexpr float c0 = xf::c_dct[0];
+  static_assert(xf::c_dct[0] == xf::c_dct[1] && xf::c_dct[0] == xf::c_dct[7], "row 0 of the basis is one value");
+  const float z = (float)dc * q0;   // dequantise (DCT.cpp:331)
+  const float u = 0.0f + c0 * z;    // stage 1: the k = 0 term
+  float S = 0.0f + u * c0;          // stage 2: the k = 0 term
+  S = __builtin_amdgcn_fmed3f(S, -128.0f, 127.0f);  // (as idct_rows, DCT.cpp:358-362)
+  uint32_t px = xf::bits(S + xf::kMagicPx);
+  if (__builtin_amdgcn_fractf(S) == 0.5f)
+    px = (uint32_t)((int)__builtin_truncf(S + __builtin_copysignf(xf::kHalfDown, S)) + 128);
+  return (px & 0xFFu) * 0x01010101u;
+}
+
 // Fused decoder (K5 + K6; MYYUV_DECODER=fused): the wave decodes its 64-block
 // group as K5 does, then runs K6's transform on it in 8-block units straight
 // from its registers: the unit's 8 decoding lanes write their blocks' int16
@@ -689,16 +710,7 @@ __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_idct(const uint8_
   for (int w = 1; w < 32; w++) acc |= nw[w];
   const bool isdc = D.live && acc == 0u;
   if (isdc) {
-    constexpr float c0 = xf::c_dct[0];
-    static_assert(xf::c_dct[0] == xf::c_dct[1] && xf::c_dct[0] == xf::c_dct[7], "row 0 of the basis is one value");
-    const float z = (float)(int16_t)nw[0] * sq[0];  // dequantise (DCT.cpp:331)
-    const float u = 0.0f + c0 * z;                  // stage 1: the k = 0 term
-    float S = 0.0f + u * c0;                        // stage 2: the k = 0 term
-    S = __builtin_amdgcn_fmed3f(S, -128.0f, 127.0f);  // (as idct_rows, DCT.cpp:358-362)
-    uint32_t px = xf::bits(S + xf::kMagicPx);
-    if (__builtin_amdgcn_fractf(S) == 0.5f)
-      px = (uint32_t)((int)__builtin_truncf(S + __builtin_copysignf(xf::kHalfDown, S)) + 128);
-    const uint32_t v4 = (px & 0xFFu) * 0x01010101u;
+    const uint32_t v4 = dc_block_pixels((int16_t)nw[0], sq[0]);
     const uint2 row = make_uint2(v4, v4);
 #pragma unroll
     for (uint32_t r = 0; r < 8; r++) {
@@ -766,6 +778,346 @@ __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_idct(const uint8_
   for (int k = 0; k < 8; k++)
     if (lane == (uint32_t)k && wid < 65536) g_dec_wstamps[wid * 8 + k] = dst.acc[k];
 #endif
+}
+
+// ---- span decoder -----------------------------------------------------------
+//
+// k_decode_span: the fused decoder with a wave owning a SPAN of kDecSpan
+// consecutive blocks of one plane (2, 4 or 8 of k_decode_idct's groups; grid
+// (spans of the three planes, frames); a plane's last span and its last
+// group are partial).  53 % of the bench frame's blocks are one-symbol blocks
+// whose 7-byte chunk is a closed form of the DC's low 11 bits
+// (single_chunk_words, codec_common.hpp), and in k_decode_idct they occupy
+// lanes of the table parse and the symbol loop like any other.  Here:
+//   span phase: lane l takes block 64 j + l of every group j; the size bytes
+//     of all groups are loaded together and scanned per group (the chunk's
+//     offset: the group's start from k_scan_chain plus the scan), then the
+//     first 7 bytes of every 7-byte chunk, and the blocks whose chunk IS the
+//     closed form (single_chunk_key) are finished at once: dc_block_pixels and
+//     the 8 row stores.  Every other live block whose chunk lies inside the
+//     plane's content is a "real" block: ballots and ranks compact them, in
+//     block order, into a list in LDS (index in the span, offset from the
+//     span's first chunk, size);
+//   passes: ceil(real / 64), none for a span of closed forms.  Lane l takes
+//     list entry 64 p + l; the pass stages the bytes from its first entry's
+//     chunk to its last entry's end (consecutive passes: consecutive,
+//     disjoint ranges; the closed-form chunks lying between are staged along)
+//     in k_decode_idct's rounds, parses, decodes and transforms as it does,
+//     the blocks' places taken from the list.
+// The stage is the 16-block transform tile's 4,608 B (a round still holds 17
+// longest chunks); with the list the wave's LDS stays at 8 KiB, 5 waves per
+// SIMD.  Error keys, codes and their order are k_decode_idct's (atomicMin:
+// the order of passes does not matter).
+constexpr uint32_t kSpanStageQuads = 288;
+constexpr uint32_t kSpanZeroBit = kSpanStageQuads * 128u;
+constexpr uint32_t kSpanGroups = kDecSpan / kWave;
+static_assert(sizeof(uint4) * kSpanStageQuads >= sizeof(float) * xf::kXfTile16, "the tile over the stage");
+static_assert(16 * (kSpanStageQuads - 1) >= 15 + 255, "a round holds its first chunk wherever it starts in its quad");
+// A list entry.  The offset from the span's first chunk is at most
+// (kDecSpan - 1) * 255: 16 bits up to 256 blocks.
+#if MYYUV_DEC_SPAN <= 256
+typedef uint32_t SpanEnt;
+__device__ __forceinline__ SpanEnt span_ent(uint32_t idx, uint32_t off, uint32_t s) {
+  return (off & 0xFFFFu) | (s << 16) | (idx << 24);
+}
+__device__ __forceinline__ uint32_t ent_off(SpanEnt e) { return e & 0xFFFFu; }
+__device__ __forceinline__ uint32_t ent_size(SpanEnt e) { return (e >> 16) & 0xFFu; }
+__device__ __forceinline__ uint32_t ent_idx(SpanEnt e) { return e >> 24; }
+#else
+typedef uint2 SpanEnt;
+__device__ __forceinline__ SpanEnt span_ent(uint32_t idx, uint32_t off, uint32_t s) {
+  return make_uint2(off, s | (idx << 8));
+}
+__device__ __forceinline__ uint32_t ent_off(SpanEnt e) { return e.x; }
+__device__ __forceinline__ uint32_t ent_size(SpanEnt e) { return e.y & 0xFFu; }
+__device__ __forceinline__ uint32_t ent_idx(SpanEnt e) { return e.y >> 8; }
+#endif
+
+__global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_span(const uint8_t* __restrict__ in,
+                                                   const uint32_t* __restrict__ in_size,
+                                                   uint32_t cap,
+                                                   const StreamDesc* __restrict__ desc,
+                                                   const uint32_t* __restrict__ local_off,
+                                                   const uint32_t* __restrict__ tile_pre,
+                                                   FrameGeom G, uint32_t spans_p0,
+                                                   uint32_t spans_p1, const QTables* __restrict__ qt,
+                                                   uint4* __restrict__ coef,
+                                                   uint8_t* __restrict__ frame,
+                                                   unsigned long long* __restrict__ err) {
+  __shared__ uint4 stq[kSpanStageQuads + 1 + kGposQuads];
+  __shared__ float sq[64];
+  __shared__ uint16_t s_blk[64];
+  __shared__ SpanEnt s_ent[kDecSpan];
+  const uint32_t lane = threadIdx.x;
+  // (the zero quad lies past the tile and the Q table is its own array: no
+  // pass overwrites either)
+  if (lane == 0) stq[kSpanStageQuads] = make_uint4(0u, 0u, 0u, 0u);  // (ordered by stage()'s barrier)
+  const uint32_t t = blockIdx.x;
+  const int p = t >= spans_p0 ? (t >= spans_p0 + spans_p1 ? 2 : 1) : 0;
+  // the plane's Q table by LDS-DMA (landed by the span phase's vmcnt wait)
+  __builtin_amdgcn_global_load_lds((const void*)&qt->q[p][lane], (__attribute__((address_space(3))) void*)sq, 4, 0,
+                                   0);
+  const uint32_t f = blockIdx.y;
+  const uint32_t nblk = G.cum[3];
+  const uint32_t gbase = f * nblk;
+  const uint32_t ntiles = (nblk + kScanTile - 1) / kScanTile;
+  in += (size_t)f * cap;
+  desc += f;
+  local_off += gbase;
+  tile_pre += (size_t)f * (ntiles + 1);
+  auto sel3 = [p](uint32_t a0, uint32_t a1, uint32_t a2) { return p == 0 ? a0 : (p == 1 ? a1 : a2); };
+  const uint32_t cum_p = sel3(G.cum[0], G.cum[1], G.cum[2]), cum_p1 = sel3(G.cum[1], G.cum[2], G.cum[3]);
+  const uint32_t span_in_plane = t - sel3(0u, spans_p0, spans_p0 + spans_p1);
+  const uint32_t b0 = cum_p + span_in_plane * kDecSpan;  // the span's blocks: [b0, b1) of the frame
+  const uint32_t b1 = min(b0 + kDecSpan, cum_p1);
+  // every scalar of the setup in one round trip: the descriptor, the payload
+  // size, the scan at the plane's start, at the span's group starts (a group
+  // past the span's end: the span's own start, unused) and at its end
+  const StreamDesc dsc = *desc;
+  const uint32_t isz = in_size[f];
+  const uint32_t b1c = min(b1, nblk - 1);
+  const uint32_t lo_p = local_off[cum_p], tp_p = tile_pre[cum_p / kScanTile];
+  uint32_t lo_j[kSpanGroups], tp_j[kSpanGroups];
+#pragma unroll
+  for (uint32_t j = 0; j < kSpanGroups; j++) {
+    const uint32_t gs = b0 + kWave * j < b1 ? b0 + kWave * j : b0;
+    lo_j[j] = local_off[gs];
+    tp_j[j] = tile_pre[gs / kScanTile];
+  }
+  const uint32_t lo_1 = local_off[b1c], tp_1 = tile_pre[b1c / kScanTile];
+  const uint32_t stot = tile_pre[ntiles];  // rel(nblk) = the total
+  __builtin_amdgcn_sched_barrier(0);  // (all issued before the first use waits)
+  if (dsc.bad != 0) {  // the frame's stream header is bad (k_scan_chain recorded it): nothing is decoded
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the Q table's LDS-DMA load)
+    return;
+  }
+  const uint32_t plane_pre = lo_p + tp_p;
+  const uint32_t limit = min(isz, cap);
+  const uint32_t end_scan = b1 == nblk ? stot : lo_1 + tp_1;
+  const uint32_t cpos = sel3(dsc.content_pos[0], dsc.content_pos[1], dsc.content_pos[2]);
+  const uint32_t csize = sel3(dsc.content_size[0], dsc.content_size[1], dsc.content_size[2]);
+  const uint32_t spos = sel3(dsc.sizes_pos[0], dsc.sizes_pos[1], dsc.sizes_pos[2]);
+  // the span's chunks end here (inside the declared content)
+  const uint32_t E_span = cpos + min(end_scan - plane_pre, csize);
+  const uint32_t pre0 = lo_j[0] + tp_j[0] - plane_pre;  // the span's first chunk in the plane's content
+
+  xf::Unit U;
+  U.p = p;
+  U.cum = cum_p;
+  U.nb = cum_p1 - cum_p;
+  U.poff = sel3(G.poff[0], G.poff[1], G.poff[2]);
+  U.pw = sel3(G.pw[0], G.pw[1], G.pw[2]);
+  U.bw = sel3(G.bw[0], G.bw[1], G.bw[2]);
+  U.bmag = p == 0 ? G.bmag[0] : (p == 1 ? G.bmag[1] : G.bmag[2]);
+  U.local0 = 0;
+  uint8_t* fr = frame + (size_t)f * G.fbytes;
+
+  // ---- span phase: sizes, offsets, the closed forms, the real list
+  uint32_t sz[kSpanGroups], rel[kSpanGroups];
+  bool ok[kSpanGroups];
+#pragma unroll
+  for (uint32_t j = 0; j < kSpanGroups; j++) {  // (all size bytes' loads together)
+    const uint32_t g = b0 + kWave * j + lane;
+    sz[j] = in[spos + ((g < b1 ? g : b1 - 1) - cum_p)];
+  }
+  bool over = false;
+#pragma unroll
+  for (uint32_t j = 0; j < kSpanGroups; j++) {
+    const bool live = b0 + kWave * j + lane < b1;
+    const uint32_t s = live ? sz[j] : 0u;
+    // (by DPP, the whole wave active: uniform control flow up to here)
+    rel[j] = lo_j[j] + tp_j[j] - plane_pre + wave_incl_scan(s) - s;
+    // plane-level check (DCT.cpp:21-33 reads past content_size otherwise):
+    // the chunks must fit the declared content
+    ok[j] = live && rel[j] + s <= csize;
+    over = over || (live && !ok[j]);
+  }
+  if (over) record_error(err, 2ull * ((uint64_t)G.fbase * nblk + gbase + cum_p), 9 /* MYYUV_E_PLANE_CONTENT */);
+  // the 7-byte chunks' bytes 0..3 and 3..6, all loads together (the other
+  // lanes read the slot's first bytes: no branch around the loads)
+  uint32_t hw[kSpanGroups], tw[kSpanGroups];
+  bool cand[kSpanGroups];
+#pragma unroll
+  for (uint32_t j = 0; j < kSpanGroups; j++) {
+    cand[j] = ok[j] && sz[j] == kSingleChunk && cpos + rel[j] + kSingleChunk <= limit;
+    const uint8_t* a = in + (cand[j] ? cpos + rel[j] : 0u);
+    __builtin_memcpy(&hw[j], a, 4);
+    __builtin_memcpy(&tw[j], a + 3, 4);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (and the Q table)
+  const float q0 = sq[0];
+  uint32_t nreal = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < kSpanGroups; j++) {
+    uint32_t key;
+    const bool single = single_chunk_key(hw[j], tw[j], key) && cand[j];
+    if (single) {
+      const uint32_t v4 = dc_block_pixels((int16_t)(((int32_t)(key << 21)) >> 21), q0);
+      const uint2 row = make_uint2(v4, v4);
+      const uint32_t local = b0 + kWave * j + lane - cum_p;
+#pragma unroll
+      for (uint32_t r = 0; r < 8; r++) *reinterpret_cast<uint2*>(fr + xf::block_row_offset(U, local, r)) = row;
+    }
+    const bool real = ok[j] && !single;
+    const uint64_t m = __ballot(real);
+    const uint32_t rank =
+        nreal + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (real) s_ent[rank] = span_ent(kWave * j + lane, rel[j] - pre0, sz[j]);
+    nreal += (uint32_t)__popcll(m);
+  }
+  xf::wave_sync();  // the list
+
+  // ---- passes over the real list
+  float* tile = reinterpret_cast<float*>(stq);
+  const uint32_t npass = (nreal + kWave - 1) / kWave;
+#pragma unroll 1
+  for (uint32_t pass = 0; pass < npass; pass++) {
+    // (the lane index made anew per pass, by mbcnt of an opaque mask with
+    // every lane active: neither it nor what derives from it, the tile and
+    // table addresses, is held in registers across the symbol loop)
+    uint32_t ones = ~0u;
+    asm volatile("" : "+s"(ones));
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(ones, __builtin_amdgcn_mbcnt_lo(ones, 0u));
+    uint32_t* gcol = reinterpret_cast<uint32_t*>(stq + kSpanStageQuads + 1) + lane;
+    const uint32_t e0 = kWave * pass, nhere = min(nreal - e0, (uint32_t)kWave);
+    const bool have = lane < nhere;
+    const SpanEnt ent = s_ent[e0 + (have ? lane : nhere - 1u)];
+    const uint32_t s = have ? ent_size(ent) : 0u;
+    const uint32_t prel = pre0 + ent_off(ent);  // the chunk in the plane's content
+    const uint32_t g = b0 + ent_idx(ent);        // the block in the frame
+    // the pass's bytes: from its first entry's chunk to its last entry's end
+    // (lanes past the last entry hold a copy of it)
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)prel);
+    const uint32_t E = min(E_span, cpos + (uint32_t)__builtin_amdgcn_readlane((int)(prel + ent_size(ent)), 63));
+    auto window = [&](uint32_t A, uint32_t& aw, uint32_t& wend, uint32_t& nq, uint32_t& nfull) {
+      aw = A & ~15u;
+      wend = aw + 16 * (kSpanStageQuads - 1);
+      nq = E > aw ? (min(E, wend) - aw + 15) >> 4 : 0u;
+      nfull = limit >= aw ? min(nq, (limit - aw) >> 4) : 0u;  // quads below limit
+    };
+    auto load4 = [&](uint32_t aw, uint32_t nfull) {  // (as decode_group's: every address below `limit`)
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        const uint32_t o = nfull > 0 ? aw + 16 * min(lane + 64u * m, nfull - 1) : 0u;
+        __builtin_amdgcn_global_load_lds((const void*)(in + o),
+                                         (__attribute__((address_space(3))) void*)(stq + 64 * m), 16, 0, 0);
+      }
+    };
+    uint32_t aw, wend, nq, nfull;
+    window(cpos + first, aw, wend, nq, nfull);
+    __syncthreads();  // the last pass's tile is read
+    load4(aw, nfull);
+    auto stage = [&]() {  // (decode_group's)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // load4's LDS writes (before the zero quads)
+      for (uint32_t k = lane + 256; k < nfull; k += 64)
+        stq[k] = *reinterpret_cast<const uint4*>(in + aw + 16 * k);
+      for (uint32_t k = nfull + lane; k <= nq; k += 64) {
+        uint32_t v[4] = {0, 0, 0, 0};
+        if (k < nq) {
+#pragma unroll
+          for (uint32_t b = 0; b < 16; b++) {
+            const uint32_t a = aw + 16 * k + b;
+            if (a < limit) v[b >> 2] |= (uint32_t)in[a] << (8 * (b & 3));
+          }
+        }
+        stq[k] = make_uint4(v[0], v[1], v[2], v[3]);
+      }
+      __syncthreads();
+    };
+    uint32_t nw[32];
+#pragma unroll
+    for (int w = 0; w < 32; w++) nw[w] = 0;
+    int code = 0;
+    bool direct = false;  // block written by decode_general
+    uint64_t pending = __ballot(have);
+    stage();
+    while (pending) {  // rounds, as decode_group's: every round retires at least the lowest pending lane
+      const bool mine = ((pending >> lane) & 1) && cpos + prel + s <= wend;
+      const LdsChunk lc{reinterpret_cast<const uint32_t*>(stq), mine ? cpos + prel - aw : 0u};
+      Table T;
+      const int pcode = parse_table(lc, mine ? s : 0u, T, gcol);
+      const bool go = mine && pcode == 0;
+      int dcode = 0;
+      const bool failed = decode_regular<kSpanZeroBit>(lc, T, gcol, go && T.regular, nw);
+      if (go && (!T.regular || failed)) {
+        direct = true;
+        dcode = decode_general(lc, T, coef, gbase + g);
+      }
+      if (mine) code = go ? dcode : pcode;
+      pending &= ~__ballot(mine);
+      if (pending) {  // the next round, from the lowest pending lane's chunk
+        __syncthreads();  // it overwrites the stage
+        const int lo = __ffsll((long long)pending) - 1;
+        window(cpos + (uint32_t)__builtin_amdgcn_readlane((int)prel, lo), aw, wend, nq, nfull);
+        load4(aw, nfull);
+        stage();
+      }
+    }
+    if (have && code) record_error(err, 2ull * ((uint64_t)G.fbase * nblk + gbase + g) + 1, code);
+    if (have && direct) {  // decode_general wrote the block to coef (a table the reference never writes)
+#pragma unroll
+      for (int c = 0; c < 8; c++) {
+        const uint4 v = coef[coef_quad(gbase + g, c)];
+        nw[4 * c] = v.x;
+        nw[4 * c + 1] = v.y;
+        nw[4 * c + 2] = v.z;
+        nw[4 * c + 3] = v.w;
+      }
+    }
+    // ---- K6 on the pass, as k_decode_idct's on its group
+    uint32_t acc = nw[0] & 0xFFFF0000u;
+#pragma unroll
+    for (int w = 1; w < 32; w++) acc |= nw[w];
+    const bool isdc = have && acc == 0u;
+    if (isdc) {
+      const uint32_t v4 = dc_block_pixels((int16_t)nw[0], sq[0]);
+      const uint2 row = make_uint2(v4, v4);
+#pragma unroll
+      for (uint32_t r = 0; r < 8; r++) *reinterpret_cast<uint2*>(fr + xf::block_row_offset(U, g - cum_p, r)) = row;
+    }
+    const uint64_t rest = __ballot(have && !isdc);
+    const uint32_t nrest = (uint32_t)__popcll(rest);
+    const uint32_t rrank =
+        __builtin_amdgcn_mbcnt_hi((uint32_t)(rest >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rest, 0u));
+    if (have && !isdc) s_blk[rrank] = (uint16_t)ent_idx(ent);  // compacted position -> the block in the span
+#pragma unroll 1
+    for (uint32_t base = 0; base < nrest;) {
+      const bool wide = nrest - base > 8u;
+      const uint32_t span = wide ? 16u : 8u, stride = wide ? (uint32_t)xf::kTile : (uint32_t)xf::kTile8;
+      const uint32_t sl = rrank - base;
+      if (have && !isdc && rrank >= base && sl < span) {
+        uint4* img = reinterpret_cast<uint4*>(tile + sl * stride + (wide ? xf::img_word(sl) : 0u));
+#pragma unroll
+        for (int c = 0; c < 8; c++) img[c] = make_uint4(nw[4 * c], nw[4 * c + 1], nw[4 * c + 2], nw[4 * c + 3]);
+      }
+      if (lane < span && base + lane >= nrest) {
+        uint4* img = reinterpret_cast<uint4*>(tile + lane * stride + (wide ? xf::img_word(lane) : 0u));
+#pragma unroll
+        for (int c = 0; c < 8; c++) img[c] = make_uint4(0u, 0u, 0u, 0u);
+      }
+      xf::wave_sync();
+      if (wide) {
+        const uint32_t q = lane & 3u, b = lane >> 2;
+        uint2 w0, w1;
+        xf::idct_rows(tile + b * xf::kTile, q, b, sq, w0, w1);
+        if (base + b < nrest) {
+          const uint32_t off = xf::block_row_offset(U, b0 - cum_p + s_blk[base + b], 2u * q);
+          *reinterpret_cast<uint2*>(fr + off) = w0;
+          *reinterpret_cast<uint2*>(fr + off + U.pw) = w1;
+        }
+      } else {
+        const uint32_t r = lane & 7u, b = lane >> 3;
+        float qc[8];  // the lane's column of the plane's Q table, Q[k][r]
+#pragma unroll
+        for (int k = 0; k < 8; k++) qc[k] = sq[8 * k + r];
+        const uint2 w = xf::idct_row8(tile + b * xf::kTile8, r, qc);
+        if (base + b < nrest)
+          *reinterpret_cast<uint2*>(fr + xf::block_row_offset(U, b0 - cum_p + s_blk[base + b], r)) = w;
+      }
+      xf::wave_sync();  // the next unit rewrites the tile
+      base += span;
+    }
+  }
 }
 
 // ---- region decode --------------------------------------------------------

@@ -431,6 +431,14 @@ int launch_decompress(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_in,
                  t1 = ceil_div(G.cum[2] - G.cum[1], kWave),
                  t2 = ceil_div(G.cum[3] - G.cum[2], kWave);
   if (c->fused_dec) {  // K5 + K6 in one pass, the coefficients kept on chip
+    if ((uint64_t)(t0 + t1 + t2) * nf >= c->dec_span_min) {  // a wave per span (same kernel id)
+      const uint32_t s0 = ceil_div(G.cum[1] - G.cum[0], kDecSpan), s1 = ceil_div(G.cum[2] - G.cum[1], kDecSpan),
+                     s2 = ceil_div(G.cum[3] - G.cum[2], kDecSpan);
+      e |= launch(c, MYYUV_K_HUFF_DEC, k_decode_span, dim3(s0 + s1 + s2, nf), dim3(kWave), s, in, d_size, cap,
+                  (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, s0, s1,
+                  qt, c->coef.as<uint4>(), static_cast<uint8_t*>(d_out), err);
+      return e ? MYYUV_E_HIP : 0;
+    }
     e |= launch(c, MYYUV_K_HUFF_DEC, k_decode_idct, dim3(t0 + t1 + t2, nf), dim3(kWave), s, in, d_size, cap,
                 (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, t0, t1,
                 qt, c->coef.as<uint4>(), static_cast<uint8_t*>(d_out), err);
@@ -806,6 +814,11 @@ int myyuv_hip_create(int device, myyuv_hip_handle* out) {
         c->fused = v && std::strcmp(v, "fused") == 0;
         const char* d = std::getenv("MYYUV_DECODER");
         c->fused_dec = !(d && std::strcmp(d, "split") == 0);
+        // fused (or unset): spans from dec_span_min groups on; span / group: always / never
+        if (const char* m = std::getenv("MYYUV_DEC_SPAN_MIN"))
+          c->dec_span_min = (uint32_t)std::strtoul(m, nullptr, 10);
+        if (d && std::strcmp(d, "span") == 0) c->dec_span_min = 0;
+        if (d && std::strcmp(d, "group") == 0) c->dec_span_min = ~0u;
       }
       // tuning knobs (diagnostic; default 100): K1 / K6 grids as a percentage
       // of the resident workgroups, leaving wave slots to other launch groups
