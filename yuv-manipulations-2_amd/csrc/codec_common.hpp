@@ -182,6 +182,14 @@ struct RequantTables {
   float qd[3][64];
 };
 
+// The downscaler's tables (a device buffer of their own; k_downscale stages the
+// wave's plane into LDS): the source quality's Q tables as QTables::q, and the
+// destination quality's QTables whole (K1's reciprocals and row bounds).
+struct DownscaleTables {
+  float qs[3][64];
+  QTables d;
+};
+
 // K1's near-tie window per unit of |t| (k_transform.hip): t = y * fl(1/Q)
 // may differ from fl(y / Q) by |t| * 1.5 * 2^-23; 2^-21 covers it with margin
 // (tools/check_numerics.c checks every Q at every tie; 2^-24 already fails).

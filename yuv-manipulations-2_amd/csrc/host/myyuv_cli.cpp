@@ -30,6 +30,10 @@
 // (transform, include/myyuv_hip.h; -q: re-encoded at those qualities on the
 // way, otherwise at its own):
 //   myyuv_cli in.myyuv -transform flip_h|flip_v|rot180|transpose|transverse|rot90|rot270 [-q q [q [q]]] -o out.myyuv
+// a compressed input at 1/2, 1/4 or 1/8 size, still compressed (downscale,
+// include/myyuv_hip.h: the stream compress would write for the scaled decode,
+// the small frame never in memory; -q: at those qualities, otherwise its own):
+//   myyuv_cli in.myyuv -downscale 1/2|1/4|1/8 [-q q [q [q]]] -o out.myyuv
 // a rectangle of a compressed input, still compressed, and a grid of
 // compressed tiles as one compressed image (crop and join, include/myyuv_hip.h:
 // byte gathers of the chunks, nothing decoded; -crop directly after the image
@@ -96,6 +100,8 @@ void usage() {
             << "  myyuv_cli IMAGE.myyuv -transform flip_h|flip_v|rot180|transpose|transverse|rot90|rot270"
                " [-q Q [Q [Q]]] -o OUT.myyuv\n"
             << "      (a compressed image mirrored, rotated or transposed, straight from its DCT coefficients)\n"
+            << "  myyuv_cli IMAGE.myyuv -downscale 1/2|1/4|1/8 [-q Q [Q [Q]]] -o OUT.myyuv\n"
+            << "      (a compressed image at that size, still compressed, straight from its DCT coefficients)\n"
             << "  myyuv_cli IMAGE.myyuv -crop X Y W H -o OUT.myyuv\n"
             << "      (a compressed image's rectangle, still compressed: its chunks, untouched)\n"
             << "  myyuv_cli -join COLS ROWS -o OUT.myyuv TILE.myyuv...\n"
@@ -434,6 +440,46 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
       out = myyuvDCT::transform_DCT_planar(yuv, op, {q[0], q[1], q[2]});
     });
     std::cout << "YUV DCT transform (" << label << ") : " << ms << " ms\n";
+    out.dump(args[a]);
+    return 0;
+  }
+  if (cmd == "-downscale") {  // 1/2|1/4|1/8 [-q Q [Q [Q]]] -o OUT.myyuv: the qualities as -compress DCT's
+    a++;
+    uint32_t den = 0;
+    if (a < args.size()) den = args[a] == "1/2" ? 2u : (args[a] == "1/4" ? 4u : (args[a] == "1/8" ? 8u : 0u));
+    if (!den) {
+      std::cout << "Invalid argument, -downscale must be followed by `1/2`, `1/4` or `1/8`\n";
+      usage();
+      return 1;
+    }
+    if (!yuv.isCompressed()) {
+      std::cout << "Nothing to downscale, image is not compressed (-downscale needs DCT coefficients)\n";
+      return 1;
+    }
+    a++;
+    const bool with_q = a < args.size() && args[a] == "-q";
+    std::vector<std::string> params;
+    if (with_q) a++;
+    while (a < args.size() && args[a] != "-o") params.push_back(args[a++]);
+    a++;
+    if (a >= args.size() || args.size() != a + 1 || (!with_q && !params.empty())) {
+      std::cout << "Invalid argument, last arguments must be `-o /path/to/new_image.myyuv`\n";
+      usage();
+      return 1;
+    }
+    std::string label = " 1/" + std::to_string(den) + " ";
+    for (const auto& p : params) label += p + " ";
+    myyuv::YUV out;
+    const float ms = elapsed_ms([&] {
+      if (with_q) {
+        uint8_t q[3];
+        dct_qualities(params, q);
+        out = myyuvDCT::downscale_DCT_planar(yuv, den, {q[0], q[1], q[2]});
+      } else {  // the image's own (downscale_DCT_planar checks their count and range)
+        out = myyuvDCT::downscale_DCT_planar(yuv, den);
+      }
+    });
+    std::cout << "YUV DCT downscale (" << label << ") : " << ms << " ms\n";
     out.dump(args[a]);
     return 0;
   }

@@ -809,6 +809,53 @@ myyuv::YUV transform_DCT_planar(const myyuv::YUV& yuv, uint32_t op, const std::a
   return recode_DCT_planar(yuv, (int)op, params);
 }
 
+// Downscale (include/myyuv_hip.h): requantize_DCT_planar's checks on the input
+// and on the new qualities; a denom other than 2, 4 or 8 is refused here (the
+// result's size depends on it), the C ABI checks everything else.  The header
+// is compress_DCT_planar's for the scaled size and the destination qualities.
+myyuv::YUV downscale_DCT_planar(const myyuv::YUV& yuv, uint32_t denom, const std::array<uint8_t, 3>& params) {
+  using myyuv::YUV;
+  if (yuv.getFormatGroup() != YUV::FormatGroup::PLANAR)
+    throw std::runtime_error("Error decompressing: YUV must be planar");
+  if (yuv.getCompression() != YUV::Compressions::DCT)
+    throw std::runtime_error("Error this decompression is unimplemented");
+  if (yuv.header.compression_params_size != 3 || !yuv.compression_params)
+    throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
+  for (int p = 0; p < 3; p++)
+    if (yuv.compression_params[p] < 1 || yuv.compression_params[p] > 100)
+      throw std::runtime_error("Level of quality must be between 1 and 100");
+  for (uint8_t q : params)
+    if (q < 1 || q > 100) throw std::runtime_error("Level of quality must be between 1 and 100");
+  if (denom != 2 && denom != 4 && denom != 8) fail(MYYUV_E_ARG);
+  const uint32_t w = yuv.header.width, h = yuv.header.height;
+  std::vector<uint8_t> payload(myyuv_dct_payload_bound(w / denom, h / denom));
+  uint32_t size = 0;
+  int64_t bad = -1;
+  const int rc = myyuv_gpu_dct_downscale(t_codec.get(), yuv.data, yuv.header.data_size, w, h, yuv.compression_params,
+                                         denom, params.data(), payload.data(), (uint32_t)payload.size(), &size, &bad);
+  if (rc) fail(rc);
+  YUV res;
+  res.header = yuv.header;
+  res.header.width = w / denom;
+  res.header.height = h / denom;
+  res.header.compression = YUV::Compressions::DCT;
+  res.header.compression_params_size = 3;
+  res.header.compression_params_pos = sizeof(myyuv::YUVHeader);
+  res.header.data_pos = sizeof(myyuv::YUVHeader) + 3;
+  res.header.data_size = size;
+  res.compression_params = new uint8_t[3]{params[0], params[1], params[2]};
+  res.data = new uint8_t[size ? size : 1];
+  std::memcpy(res.data, payload.data(), size);
+  return res;
+}
+
+myyuv::YUV downscale_DCT_planar(const myyuv::YUV& yuv, uint32_t denom) {
+  std::array<uint8_t, 3> q = {0, 0, 0};  // (a source without three parameters: refused by the checks above)
+  if (yuv.header.compression_params_size == 3 && yuv.compression_params)
+    q = {yuv.compression_params[0], yuv.compression_params[1], yuv.compression_params[2]};
+  return downscale_DCT_planar(yuv, denom, q);
+}
+
 namespace {
 
 // The input checks of decompress_DCT_planar_region, and the header of a

@@ -170,6 +170,14 @@ myyuv::YUV requantize_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t
 // qualities `params`, no pixels in between.  Checks, messages and header as
 // requantize_DCT_planar; width and height are swapped for a swapping operation.
 myyuv::YUV transform_DCT_planar(const myyuv::YUV& yuv, uint32_t op, const std::array<uint8_t, 3>& params);
+// Downscale (include/myyuv_hip.h): the DCT-compressed (width/denom) x
+// (height/denom) frame, denom 2, 4 or 8, of a DCT-compressed frame, the small
+// frame never in memory: compress_DCT_planar(decompress_DCT_planar_scaled(yuv,
+// denom), params) bit for bit.  Without `params` the source's own qualities.
+// requantize_DCT_planar's checks on the input; compress_DCT_planar's header for
+// the scaled size and the destination qualities.
+myyuv::YUV downscale_DCT_planar(const myyuv::YUV& yuv, uint32_t denom);
+myyuv::YUV downscale_DCT_planar(const myyuv::YUV& yuv, uint32_t denom, const std::array<uint8_t, 3>& params);
 // Crop (include/myyuv_hip.h): the w x h rectangle at (x, y) of a DCT-compressed
 // frame, still compressed: its blocks' chunk bytes, gathered on the GPU.
 // requantize_DCT_planar's checks on the input; compress_DCT_planar's header

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "codec_common.hpp"
+#include "downscale.h"
 #include "k_chain.hpp"
 #include "k_stream.hpp"
 #include "myyuv_hip.h"
@@ -40,6 +41,10 @@ template <int N>
 __global__ void k_decode_scaled(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
                                 const uint32_t*, FrameGeom, uint32_t, uint32_t, const QTables*, uint4*, uint8_t*,
                                 unsigned long long*);
+template <int N>
+__global__ void k_downscale(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
+                            const uint32_t*, FrameGeom, FrameGeom, myyuv_downscale::Map, const DownscaleTables*,
+                            uint4*, uint8_t*, uint32_t*, unsigned long long*);
 __global__ void k_requant(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
                           const uint32_t*, FrameGeom, uint32_t, uint32_t, const RequantTables*, uint4*, uint8_t*,
                           uint32_t*, unsigned long long*);
@@ -226,6 +231,15 @@ struct myyuv_hip_ctx {
   bool rq_swap = false;
   uint32_t rq_eq = 0;
   DevBuf xfgen;
+  // the downscaler's tables (DownscaleTables: the source Q values and the
+  // destination's QTables), cached by the (source, destination) quality
+  // triples in a buffer of their own, as the requantiser's: qt / qtd and rq /
+  // rqt and their caches are untouched by a downscale call
+  DevBuf dst;
+  DownscaleTables ds;
+  hipStream_t ds_stream = nullptr;
+  uint8_t ds_cached[6] = {0, 0, 0, 0, 0, 0};
+  bool ds_valid = false;
   // crop and join: the output blocks' size bytes in destination order, and the
   // destination scan's group offsets and tile prefixes (the source scan's are
   // loff / tiles; the status words serve both scans, one after the other)
@@ -247,8 +261,8 @@ struct myyuv_hip_ctx {
   };
   uint32_t prof = 0;  // bit k: stamp kernel id k
   uint32_t skip = 0;  // diagnostic: bit k: do not launch kernel id k (myyuv_debug_skip_kernels)
-  double ms[MYYUV_K_LIMIT] = {};
-  int64_t launches[MYYUV_K_LIMIT] = {};
+  double ms[MYYUV_K_BOUND] = {};
+  int64_t launches[MYYUV_K_BOUND] = {};
   std::vector<Stamp> pending;
   std::vector<Event> free_events;
   // set once every piece of it exists (pipe_init)

@@ -35,8 +35,10 @@
 //   written as 8 quads of the codec_common.hpp layout that K6 reads.
 #include "codec_common.hpp"
 #include "coef_xform.h"
+#include "downscale.h"
 #include "huff_common.hpp"
 #include "idct_scaled.h"
+#include "k1_store.hpp"
 #include "k_metric.hpp"
 #include "k_stream.hpp"
 #include "requant.h"
@@ -1143,20 +1145,26 @@ __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_span(const uint8_
 // bytes comes from the wave's own scan; and blocks with a table that is not
 // "regular" are decoded (decode_general_to) into the value-position table's
 // 2 KiB of LDS, dead by then, 16 lanes at a time, and read back into nw: the
-// region path has no coefficient buffer in HBM.
+// region path has no coefficient buffer in HBM.  The rounds themselves are
+// decode_run_at, which takes the run as (plane, first block, length);
+// decode_run picks the region segment's run and names its output blocks.
 struct DecodeRun {
   uint32_t f;
   int p;
   uint32_t jo0, n;  // the run's first block in the OUTPUT plane, its length
   bool live;
 };
-__device__ __forceinline__ bool decode_run(const uint8_t* __restrict__ in, const uint32_t* __restrict__ in_size,
-                                           uint32_t cap, const StreamDesc* __restrict__ desc,
-                                           const uint32_t* __restrict__ local_off,
-                                           const uint32_t* __restrict__ tile_pre, const FrameGeom& G,
-                                           const FrameGeom& R, const RegionSegs& S,
-                                           unsigned long long* __restrict__ err, uint4* stq, DecodeRun& D,
-                                           uint32_t (&nw)[32]) {
+// decode_run's rounds for the run of n <= 64 blocks that starts at block j of
+// plane p of the source frame (wave-uniform), whoever chose it: the region
+// path's segments (decode_run below) and the downscaler's runs (k_downscale).
+// good: the lane is live and its block decoded without an error.
+__device__ __forceinline__ bool decode_run_at(const uint8_t* __restrict__ in, const uint32_t* __restrict__ in_size,
+                                              uint32_t cap, const StreamDesc* __restrict__ desc,
+                                              const uint32_t* __restrict__ local_off,
+                                              const uint32_t* __restrict__ tile_pre, const FrameGeom& G,
+                                              unsigned long long* __restrict__ err, uint4* stq, const int p,
+                                              const uint32_t j, const uint32_t n, uint32_t (&nw)[32], bool& live_out,
+                                              bool& good) {
   const uint32_t f = blockIdx.y;
   const uint32_t nblk = G.cum[3];
   const uint32_t gbase = f * nblk;
@@ -1168,18 +1176,9 @@ __device__ __forceinline__ bool decode_run(const uint8_t* __restrict__ in, const
   const uint32_t lane = threadIdx.x;
   uint32_t* gtab = reinterpret_cast<uint32_t*>(stq + kStageQuads + 1);
   uint32_t* gcol = gtab + lane;
-  const uint32_t t = blockIdx.x;
-  const int p = t >= S.scum[1] ? (t >= S.scum[2] ? 2 : 1) : 0;
   auto sel3 = [p](uint32_t a0, uint32_t a1, uint32_t a2) { return p == 0 ? a0 : (p == 1 ? a1 : a2); };
   const uint32_t cum_p = sel3(G.cum[0], G.cum[1], G.cum[2]);
-  const uint32_t spr = sel3(S.spr[0], S.spr[1], S.spr[2]);
-  const uint32_t ts = t - sel3(0u, S.scum[1], S.scum[2]);
-  const uint32_t row = ts / spr, k = ts - row * spr;
-  const uint32_t rbw = sel3(R.bw[0], R.bw[1], R.bw[2]), sbw = sel3(G.bw[0], G.bw[1], G.bw[2]);
-  const uint32_t n = min((uint32_t)kWave, rbw - kWave * k);
-  // the run's first block inside the source plane, its group's first, and
-  // the group's blocks in front of the run
-  const uint32_t j = (sel3(S.by[0], S.by[1], S.by[2]) + row) * sbw + sel3(S.bx[0], S.bx[1], S.bx[2]) + kWave * k;
+  // the run's group's first block, and the group's blocks in front of the run
   const uint32_t jg = j & ~(uint32_t)(kWave - 1), npre = j - jg;
   const bool live = lane < n;
   const uint32_t g = cum_p + j + lane;  // the lane's block in the source frame
@@ -1293,12 +1292,36 @@ __device__ __forceinline__ bool decode_run(const uint8_t* __restrict__ in, const
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every LDS-DMA load has landed (whether or not a round ran)
   if (ok && code) record_error(err, 2ull * ((uint64_t)G.fbase * nblk + gbase + g) + 1, code);
-  D.f = f;
+  live_out = live;
+  good = ok && code == 0;
+  return !bad;
+}
+
+__device__ __forceinline__ bool decode_run(const uint8_t* __restrict__ in, const uint32_t* __restrict__ in_size,
+                                           uint32_t cap, const StreamDesc* __restrict__ desc,
+                                           const uint32_t* __restrict__ local_off,
+                                           const uint32_t* __restrict__ tile_pre, const FrameGeom& G,
+                                           const FrameGeom& R, const RegionSegs& S,
+                                           unsigned long long* __restrict__ err, uint4* stq, DecodeRun& D,
+                                           uint32_t (&nw)[32]) {
+  const uint32_t t = blockIdx.x;
+  const int p = t >= S.scum[1] ? (t >= S.scum[2] ? 2 : 1) : 0;
+  auto sel3 = [p](uint32_t a0, uint32_t a1, uint32_t a2) { return p == 0 ? a0 : (p == 1 ? a1 : a2); };
+  const uint32_t spr = sel3(S.spr[0], S.spr[1], S.spr[2]);
+  const uint32_t ts = t - sel3(0u, S.scum[1], S.scum[2]);
+  const uint32_t row = ts / spr, k = ts - row * spr;
+  const uint32_t rbw = sel3(R.bw[0], R.bw[1], R.bw[2]), sbw = sel3(G.bw[0], G.bw[1], G.bw[2]);
+  const uint32_t n = min((uint32_t)kWave, rbw - kWave * k);
+  // the run's first block inside the source plane
+  const uint32_t j = (sel3(S.by[0], S.by[1], S.by[2]) + row) * sbw + sel3(S.bx[0], S.bx[1], S.bx[2]) + kWave * k;
+  bool good;
+  const bool frame_ok =
+      decode_run_at(in, in_size, cap, desc, local_off, tile_pre, G, err, stq, p, j, n, nw, D.live, good);
+  D.f = blockIdx.y;
   D.p = p;
   D.jo0 = row * rbw + kWave * k;
   D.n = n;
-  D.live = live;
-  return !bad;
+  return frame_ok;
 }
 
 __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_region(const uint8_t* __restrict__ in,
@@ -1510,6 +1533,154 @@ template __global__ void k_decode_scaled<2>(const uint8_t*, const uint32_t*, uin
 template __global__ void k_decode_scaled<4>(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
                                             const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t,
                                             const QTables*, uint4*, uint8_t*, unsigned long long*);
+
+// ---- downscale ------------------------------------------------------------
+//
+// k_downscale<N>: a DCT stream at 1/denom size from a DCT stream, N = 8 / denom
+// in {4, 2, 1} (include/myyuv_hip.h, "Downscale"): the scaled decode, K1 and
+// its exact path in one launch, the scaled frame never in HBM.  The work map is
+// downscale.h's: wave blockIdx.x of frame blockIdx.y owns a segment of a band
+// (up to 64 source block columns of the denom source block rows under one
+// output block row).
+//  - Decode: the band as denom runs, one after the other (decode_run_at: each
+//    run one contiguous byte range, one chunk per lane, the whole chunk decoded;
+//    tables that are not "regular" in the value-position table, as the region
+//    path).  After a run every lane transforms its block's N x N corner
+//    (idct_scaled_block<N>, the scaled decode's arithmetic and clamp) and
+//    writes its N rows of N bytes into the wave's pixel image: the wave's
+//    output blocks as 8 x 8-byte block images (lane_pixel).  The image is an
+//    LDS array of its own: the stage is live again in the next run.
+//  - Forward transform: the wave's n / denom output blocks in units of 16, four
+//    lanes per block (fdct_core: K1's fast path, and on a failed proof the
+//    exact path in the same wave, so there is no fix list).  The transpose tile
+//    lies over the stage, which is dead after the last run.  Each unit's quads,
+//    row masks and info words go out as K1's do (store_block_rows_buf) at the
+//    DESTINATION block index; block slots past the wave's output are dropped
+//    by the descriptors' range.
+// The zero-block rule of k_requant holds at the destination: every output
+// block belongs to exactly one wave, and the wave writes its mask and info word
+// whatever the stream holds.  A lane whose chunk failed, and every lane of a
+// frame whose header k_scan_chain rejected, contributes zero coefficients,
+// that is pixel 128; the error is in the shared error word, keyed by the
+// SOURCE block (record_error's minimum: decompress's first bad block in any
+// wave order).
+// (4 waves per SIMD: the wave's LDS, 10-11 KiB with the image and K1's tables,
+// admits 16 workgroups per CU)
+template <int N>
+__global__ __launch_bounds__(64, 4) void k_downscale(const uint8_t* __restrict__ in,
+                                                 const uint32_t* __restrict__ in_size,
+                                                 uint32_t cap,
+                                                 const StreamDesc* __restrict__ desc,
+                                                 const uint32_t* __restrict__ local_off,
+                                                 const uint32_t* __restrict__ tile_pre,
+                                                 FrameGeom G, FrameGeom Gd, myyuv_downscale::Map M,
+                                                 const DownscaleTables* __restrict__ dt,
+                                                 uint4* __restrict__ coef,
+                                                 uint8_t* __restrict__ rmask,
+                                                 uint32_t* __restrict__ binfo,
+                                                 unsigned long long* __restrict__ err) {
+  static_assert(N == 1 || N == 2 || N == 4, "1/8, 1/4 or 1/2");
+  constexpr uint32_t kDen = 8 / N;
+  // the wave's output blocks (64 / denom), and at least one 16-block unit
+  constexpr uint32_t kImgBlocks = kWave / kDen > kXfUnit ? kWave / kDen : kXfUnit;
+  static_assert(sizeof(uint4) * kStageQuads >= sizeof(float) * xf::kXfTile16,
+                "the transpose tile over the stage (dead after the last run)");
+  static_assert(kGposQuads * 16 >= 16 * 128, "16 blocks of int16[64] in the value-position table");
+  static_assert(myyuv_downscale::kSeg == kWave, "a lane per source block column");
+  static_assert(offsetof(QTables, r) == sizeof(float) * xf::kSqR && offsetof(QTables, kb) == sizeof(float) * xf::kSqKb,
+                "layout");
+  __shared__ uint4 stq[kStageQuads + 1 + kGposQuads];
+  __shared__ uint4 simg[kImgBlocks * 4];  // the pixel image: NOT over the stage, which the next run refills
+  __shared__ float sqs[64];               // the source plane's Q table
+  __shared__ float sqr[xf::kSqWords];     // the destination's QTables (the wave's plane filled in)
+  __shared__ uint4 szz[8];
+  const uint32_t lane = threadIdx.x;
+  const myyuv_downscale::Wave W = myyuv_downscale::wave_of(M, blockIdx.x);
+  const int p = W.p;
+  if (lane == 0) stq[kStageQuads] = make_uint4(0u, 0u, 0u, 0u);  // (ordered by decode_run_at's barrier)
+  // the plane's tables by LDS-DMA (landed by decode_run_at's final vmcnt wait)
+  __builtin_amdgcn_global_load_lds((const void*)&dt->qs[p][lane], (__attribute__((address_space(3))) void*)sqs, 4, 0,
+                                   0);
+  __builtin_amdgcn_global_load_lds((const void*)&dt->d.q[p][lane],
+                                   (__attribute__((address_space(3))) void*)(sqr + p * 64), 4, 0, 0);
+  __builtin_amdgcn_global_load_lds((const void*)&dt->d.r[p][lane],
+                                   (__attribute__((address_space(3))) void*)(sqr + xf::kSqR + p * 64), 4, 0, 0);
+  if (lane < 8) sqr[xf::kSqKb + p * 8 + lane] = dt->d.kb[p][lane];
+  xf::stage_zz(szz);
+  // pixel 128 everywhere: block slots past the wave's output are transformed
+  // with the rest of their unit
+  for (uint32_t i = lane; i < kImgBlocks * 4; i += kWave)
+    simg[i] = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
+  uint8_t* img = reinterpret_cast<uint8_t*>(simg);
+
+#pragma unroll 1
+  for (uint32_t r = 0; r < kDen; r++) {
+    if (r != 0) __syncthreads();  // the run's loads overwrite the stage
+    uint32_t nw[32];
+#pragma unroll
+    for (int w = 0; w < 32; w++) nw[w] = 0;
+    bool live, good;
+    (void)decode_run_at(in, in_size, cap, desc, local_off, tile_pre, G, err, stq, p,
+                        myyuv_downscale::run_first(M, W, r), W.n, nw, live, good);
+    // the corner's coefficients, natural order (see k_decode_scaled); a lane
+    // that is not `good` (a failed chunk: partial symbols; a rejected frame; a
+    // lane past the run) takes zeros
+    int16_t z[N * N];
+    float q[N * N];
+#pragma unroll
+    for (int u = 0; u < N; u++) {
+      const uint32_t w0 = good ? nw[4 * u] : 0u, w1 = good ? nw[4 * u + 1] : 0u;
+#pragma unroll
+      for (int v = 0; v < N; v++) {
+        const uint32_t w = v < 2 ? w0 : w1;
+        z[u * N + v] = (int16_t)((v & 1) ? w >> 16 : w & 0xFFFFu);
+        q[u * N + v] = sqs[8 * u + v];
+      }
+    }
+    uint8_t px[N * N];
+    myyuv_scaled::idct_scaled_block<N>(z, q, px);
+    if (live) {
+#pragma unroll
+      for (int i = 0; i < N; i++) {
+        uint8_t* o = img + myyuv_downscale::lane_pixel(kDen, r, lane, (uint32_t)i);
+        if constexpr (N == 1) {
+          o[0] = px[0];
+        } else if constexpr (N == 2) {
+          *reinterpret_cast<uint16_t*>(o) = (uint16_t)(px[2 * i] | (px[2 * i + 1] << 8));
+        } else {
+          *reinterpret_cast<uint32_t*>(o) = (uint32_t)px[4 * i] | ((uint32_t)px[4 * i + 1] << 8) |
+                                            ((uint32_t)px[4 * i + 2] << 16) | ((uint32_t)px[4 * i + 3] << 24);
+        }
+      }
+    }
+  }
+  xf::wave_sync();  // the image is complete; the stage is dead
+
+  // ---- K1's per-unit body on the wave's output blocks, lane (b, q)
+  const uint32_t q = lane & 3u, b = lane >> 2;
+  float* tb = reinterpret_cast<float*>(stq) + b * xf::kTile;
+  const xf::K1Rsrc rs = xf::k1_rsrc(coef, rmask, binfo, Gd);
+  const uint32_t g0 = blockIdx.y * Gd.cum[3] + (p == 0 ? Gd.cum[0] : (p == 1 ? Gd.cum[1] : Gd.cum[2]));
+#pragma unroll 1
+  for (uint32_t u0 = 0; u0 < W.nout; u0 += kXfUnit) {
+    const uint32_t slot = u0 + b;  // (< kImgBlocks: nout <= 64 / denom)
+    const bool lv = slot < W.nout;
+    const uint32_t g = g0 + myyuv_downscale::out_block(W, slot);
+    xf::fdct_core(img + 64u * slot, tb, q, sqr, p, [&](const uint32_t (&c)[16], bool keep) {
+      xf::store_block_rows_buf(c, q, lv && keep, g, rs, szz + 2 * q);
+    });
+    xf::wave_sync();  // the next unit rewrites the tile
+  }
+}
+#define MYYUV_DOWNSCALE_INST(N)                                                                                   \
+  template __global__ void k_downscale<N>(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,           \
+                                          const uint32_t*, const uint32_t*, FrameGeom, FrameGeom,                 \
+                                          myyuv_downscale::Map, const DownscaleTables*, uint4*, uint8_t*,         \
+                                          uint32_t*, unsigned long long*);
+MYYUV_DOWNSCALE_INST(1)
+MYYUV_DOWNSCALE_INST(2)
+MYYUV_DOWNSCALE_INST(4)
+#undef MYYUV_DOWNSCALE_INST
 
 // ---- requantise -----------------------------------------------------------
 //

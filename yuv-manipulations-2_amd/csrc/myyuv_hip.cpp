@@ -9,6 +9,7 @@
 //   compare:    parse -> scan -> decode_compare (every block, against a reference frame's rows);
 //               two raw frames: frame_compare
 //   requantise: parse -> scan -> requant (decode + rescale) -> K2 (+ overflow pass) -> K4
+//   downscale:  parse -> scan -> downscale (decode + scaled IDCT + K1's FDCT) -> K2 (+ overflow pass) -> K4
 //   transform:  parse -> scan -> coef_xform (decode + move + rescale) -> K2 (+ overflow pass) -> K4
 //   crop, join: parse -> scan -> gather_sizes -> scan -> gather_heads -> stream_gather (bytes only)
 // Every launch goes to one stream; nothing synchronises inside the
@@ -627,6 +628,76 @@ int launch_coef_xform(myyuv_hip_ctx* c, const FrameGeom& G, const FrameGeom& Gd,
                       const uint32_t* d_size_in, uint32_t cap_in, void* d_out, uint32_t cap_out,
                       uint32_t* d_size_out, hipStream_t s) {
   return launch_recode(c, G, Gd, (int)op, d_in, d_size_in, cap_in, d_out, cap_out, d_size_out, s);
+}
+
+// The downscaler's tables for (q_src, q_dst), on the device in stream order;
+// cached by the six quality bytes as set_requant_tables caches its pair.  The
+// other calls' tables (qt / qtd, rq / rqt) and their caches are not touched.
+int set_downscale_tables(myyuv_hip_ctx* c, const uint8_t qs[3], const uint8_t qd[3], hipStream_t s) {
+  uint8_t key[6];
+  std::memcpy(key, qs, 3);
+  std::memcpy(key + 3, qd, 3);
+  if (c->ds_valid && std::memcmp(c->ds_cached, key, 6) == 0 && c->ds_stream == s) return 0;
+  c->ds_valid = false;  // (until the new tables are queued)
+  for (int p = 0; p < 3; p++) {
+    make_qtable(qs[p], p != 0, c->ds.qs[p]);
+    make_qtable(qd[p], p != 0, c->ds.d.q[p]);
+  }
+  finish_qtables(c->ds.d, 3);
+  if (c->dst.grow(sizeof(DownscaleTables))) return MYYUV_E_HIP;
+  // kernels queued on another stream may still read the old tables
+  if (c->ds_stream && c->ds_stream != s && hipStreamSynchronize(c->ds_stream) != hipSuccess) return MYYUV_E_HIP;
+  if (hipMemcpyAsync(c->dst.p, &c->ds, sizeof(DownscaleTables), hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  c->ds_stream = s;
+  std::memcpy(c->ds_cached, key, 6);
+  c->ds_valid = true;
+  return 0;
+}
+
+// Downscale (include/myyuv_hip.h): stream f of G's frames at d_in + f * cap_in
+// -> the stream of the 1/denom-size frame (geometry Gd, the same batch) at
+// d_out + f * cap_out.  The scan as launch_decompress runs it on the source;
+// k_downscale<8 / denom> decodes every block, builds the scaled pixels in LDS
+// and leaves K1's hand-off for the destination's blocks; then the encoder from
+// K2 on with Gd, as launch_recode runs it.  work[0] is zeroed here as K1 would
+// have.  No scaled frame, no K1, no fix kernel.  Workspace: reserve_downscale.
+int reserve_downscale(myyuv_hip_ctx* c, const FrameGeom& G, const FrameGeom& Gd) {
+  if (int e = reserve_scan(c, G)) return e;  // (the source's; reserve's own, for Gd, is smaller)
+  return reserve(c, Gd);
+}
+
+int launch_downscale(myyuv_hip_ctx* c, const FrameGeom& G, const FrameGeom& Gd, uint32_t denom, const void* d_in,
+                     const uint32_t* d_size_in, uint32_t cap_in, void* d_out, uint32_t cap_out,
+                     uint32_t* d_size_out, hipStream_t s) {
+  const uint32_t nf = G.nframes;
+  const uint32_t ntiles = ceil_div(G.cum[3], kScanTile);
+  unsigned long long* err = c->err.as<unsigned long long>();
+  StreamDesc* desc = c->desc.as<StreamDesc>();
+  const uint8_t* in = static_cast<const uint8_t*>(d_in);
+  int e = 0;
+  ScanSrc SS;
+  for (int i = 0; i < 4; i++) SS.cum[i] = G.cum[i];
+  for (int p = 0; p < 3; p++) SS.pos[p] = 0;
+  e |= launch(c, MYYUV_K_SCAN, k_scan_chain, dim3(ntiles, nf), dim3(256), s, in, cap_in, SS, d_size_in, cap_in, G,
+              desc, c->loff.as<uint32_t>(), c->tiles.as<uint32_t>(), ntiles, c->status.as<unsigned long long>(),
+              next_epoch(c), err);
+  e |= hipMemsetAsync(c->work.p, 0, 4, s) != hipSuccess;
+  const myyuv_downscale::Map M = myyuv_downscale::make_map(G.pw[0], G.ph[0], denom);
+  auto* k = denom == 2 ? k_downscale<4> : (denom == 4 ? k_downscale<2> : k_downscale<1>);
+  e |= launch(c, MYYUV_K_DOWNSCALE, k, dim3(M.wcum[3], nf), dim3(kWave), s, in, d_size_in, cap_in,
+              (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, Gd, M,
+              c->dst.as<const DownscaleTables>(), c->coef.as<uint4>(), c->rmask.as<uint8_t>(),
+              c->binfo.as<uint32_t>(), err);
+  e |= launch_huff_encode(c, Gd, s);
+  e |= launch(c, MYYUV_K_SCAN, k_tile_scan, dim3(nf), dim3(256), s, c->tinfo.as<uint32_t>(), Gd,
+              static_cast<uint8_t*>(d_out), cap_out, d_size_out, err);
+  const uint32_t W = k2_win(nf * Gd.tcum[3]);  // (K2's windows, as launch_compress)
+  e |= launch(c, MYYUV_K_COMPACT, k_stream_out, dim3(ceil_div(Gd.tcum[3] * nf, 8 * W) * 8 * W), dim3(256), s,
+              c->stage.as<const uint32_t>(), c->tinfo.as<const uint32_t>(), c->sizes.as<const uint8_t>(),
+              c->srcoff.as<const uint32_t>(), c->oslots.as<const uint32_t>(), Gd, static_cast<uint8_t*>(d_out),
+              cap_out, W);
+  return e ? MYYUV_E_HIP : 0;
 }
 
 // The transform's scratch coefficient image (decode_general's blocks, in
@@ -1923,6 +1994,85 @@ int myyuv_gpu_dct_transform_device(myyuv_hip_handle c, const void* d_payload, co
                        d_out_sizes, stream);
 }
 
+// ---- downscale (defined in myyuv_hip.h) -------------------------------------
+int myyuv_gpu_dct_downscale(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                            const uint8_t q_src[3], uint32_t denom, const uint8_t q_dst[3], uint8_t* out,
+                            uint32_t cap, uint32_t* out_size, int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payload || !out || !out_size || !q_src || !q_dst) return MYYUV_E_ARG;
+  int e = check_q(q_src);
+  if (e) return e;
+  FrameGeom G, Gd;
+  if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G)) || (e = check_q(q_dst))) return e;
+  if (!denom_ok(denom)) return MYYUV_E_ARG;
+  if ((e = make_geom(w / denom, h / denom, Gd))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const uint32_t cap_in = (size + 3) & ~3u;
+  // the device writes into a buffer of the bound's size, so a result larger
+  // than the caller's `cap` is known by its size alone (as compress)
+  const uint32_t bound = myyuv_dct_payload_bound(w / denom, h / denom);
+  if ((e = reserve_downscale(c, G, Gd)) || (e = set_downscale_tables(c, q_src, q_dst, s))) return e;
+  if (c->rqsrc.grow(cap_in) || c->payload.grow(bound) || c->psize.grow(8)) return MYYUV_E_HIP;
+  uint32_t* psz = c->psize.as<uint32_t>();  // [0] the source's size, [1] the result's
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (hipMemsetAsync(static_cast<uint8_t*>(c->rqsrc.p) + (cap_in - 4), 0, 4, s) != hipSuccess ||
+      h2d(c->rqsrc.p, payload, size, s) || hipMemcpyAsync(psz, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  if ((e = launch_downscale(c, G, Gd, denom, c->rqsrc.p, psz, cap_in, c->payload.p, bound, psz + 1, s))) return e;
+  uint32_t nout = 0;
+  if (hipMemcpyAsync(&nout, psz + 1, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return MYYUV_E_HIP;
+  if ((e = read_err(c, s, bad_block))) {  // (synchronises)
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  *out_size = nout;
+  if (nout > cap) return MYYUV_E_CAPACITY;
+  if (d2h(out, c->payload.p, nout, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+int myyuv_gpu_dct_downscale_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_payload_sizes,
+                                   uint32_t cap_in, uint32_t nframes, uint32_t w, uint32_t h,
+                                   const uint8_t q_src[3], uint32_t denom, const uint8_t q_dst[3], void* d_out,
+                                   uint32_t cap_out, uint32_t* d_out_sizes, void* stream) {
+  if (!c || !d_payload || !d_payload_sizes || !d_out || !d_out_sizes || !q_src || !q_dst) return MYYUV_E_ARG;
+  FrameGeom G, Gd;
+  int e = check_q(q_src);
+  if (e || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes)) || (e = check_q(q_dst))) return e;
+  if (!denom_ok(denom)) return MYYUV_E_ARG;
+  if ((e = make_geom(w / denom, h / denom, Gd))) return e;
+  if (((uintptr_t)d_payload & 3) || ((uintptr_t)d_out & 3) || (nframes > 1 && ((cap_in | cap_out) & 3)))
+    return MYYUV_E_ARG;
+  {  // the two stream arrays must not overlap: K4 writes frame f while later frames are still being read
+    const uintptr_t a = (uintptr_t)d_payload, b = (uintptr_t)d_out;
+    const uint64_t na = (uint64_t)cap_in * nframes, nb = (uint64_t)cap_out * nframes;
+    if (a < b + nb && b < a + na) return MYYUV_E_ARG;
+  }
+  Entry en(c, stream);
+  // (as several launches past the kernels' 32-bit block numbers or the grid's 65,535 frames)
+  const uint32_t per = std::min(launch_frames(G, c->launch_blocks), 65535u);
+  FrameGeom GL = G, GD = Gd;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = set_batch(GD, std::min(nframes, per))) ||
+      (e = reserve_downscale(c, GL, GD)) || (e = set_downscale_tables(c, q_src, q_dst, en.s)))
+    return e;
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GD = Gd;
+    GL.fbase = GD.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0))) || (e = set_batch(GD, std::min(per, nframes - f0))))
+      return e;
+    const uint8_t* src = static_cast<const uint8_t*>(d_payload) + (size_t)f0 * cap_in;
+    uint8_t* dst = static_cast<uint8_t*>(d_out) + (size_t)f0 * cap_out;
+    if ((e = launch_downscale(c, GL, GD, denom, src, d_payload_sizes + f0, cap_in, dst, cap_out, d_out_sizes + f0,
+                              en.s)))
+      return e;
+  }
+  return 0;
+}
+
 // ---- crop and join (defined in myyuv_hip.h) ---------------------------------
 namespace {
 
@@ -2461,7 +2611,7 @@ int myyuv_gpu_dct_decompress_to_bmp_frames(myyuv_hip_handle c, const uint8_t* co
 }
 
 int myyuv_hip_profile(myyuv_hip_handle c, int enable) {
-  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_LIMIT) - 1u : 0u);
+  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_BOUND) - 1u : 0u);
 }
 
 int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
@@ -2470,8 +2620,8 @@ int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
   DeviceGuard g(c->device);
   (void)hipStreamSynchronize(c->stream);
   drain_profile(c);
-  c->prof = mask & ((1u << MYYUV_K_LIMIT) - 1u);
-  for (int k = 0; k < MYYUV_K_LIMIT; k++) {
+  c->prof = mask & ((1u << MYYUV_K_BOUND) - 1u);
+  for (int k = 0; k < MYYUV_K_BOUND; k++) {
     c->ms[k] = 0;
     c->launches[k] = 0;
   }
@@ -2484,8 +2634,8 @@ int myyuv_hip_kernel_stats_n(myyuv_hip_handle c, uint32_t n, double* ms, int64_t
   DeviceGuard g(c->device);
   drain_profile(c);
   for (uint32_t k = 0; k < n; k++) {
-    ms[k] = k < MYYUV_K_LIMIT ? c->ms[k] : 0.0;
-    launches[k] = k < MYYUV_K_LIMIT ? c->launches[k] : 0;
+    ms[k] = k < MYYUV_K_BOUND ? c->ms[k] : 0.0;
+    launches[k] = k < MYYUV_K_BOUND ? c->launches[k] : 0;
   }
   return 0;
 }

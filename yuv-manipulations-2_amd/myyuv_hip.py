@@ -36,11 +36,15 @@ K_COMPARE = KERNELS_ALL.index("decode_compare")
 K_FRAME_CMP = KERNELS_ALL.index("frame_compare")
 K_METRIC_SUM = KERNELS_ALL.index("metric_reduce")
 K_END = len(KERNELS_ALL)  # MYYUV_K_END: frozen like the two bounds before it; the ids after it end at K_LIMIT
-# every kernel: Codec.profile / Codec.kernel_stats take and return these names (KERNELS_ALL's and the probe's)
+# KERNELS_ALL's names and the probe's
 KERNELS_EVERY = KERNELS_ALL + ["coef_compare", "probe_out"]
 K_COEF_CMP = KERNELS_EVERY.index("coef_compare")
 K_PROBE_OUT = KERNELS_EVERY.index("probe_out")
-K_LIMIT = len(KERNELS_EVERY)  # MYYUV_K_LIMIT
+K_LIMIT = len(KERNELS_EVERY)  # MYYUV_K_LIMIT: frozen like the bounds before it; the ids after it end at K_BOUND
+# the downscaler's id follows; Codec.profile / Codec.kernel_stats take and return KERNELS_FULL's names
+KERNELS_FULL = KERNELS_EVERY + ["downscale"]
+K_DOWNSCALE = KERNELS_FULL.index("downscale")
+K_BOUND = len(KERNELS_FULL)  # MYYUV_K_BOUND
 E_TARGET = 18  # MYYUV_E_TARGET: "target not reachable" (error_message; strerror's table ends at 17)
 PROBE_SIZE, PROBE_METRIC = 1, 2  # MYYUV_PROBE_*
 # myyuv_block_metric, as the maps of the compare calls come back
@@ -74,6 +78,7 @@ EXPORTS = [
     "myyuv_gpu_dct_decompress_scaled_to_bmp",
     "myyuv_gpu_dct_requantize", "myyuv_gpu_dct_requantize_device",
     "myyuv_gpu_dct_transform", "myyuv_gpu_dct_transform_device",
+    "myyuv_gpu_dct_downscale", "myyuv_gpu_dct_downscale_device",
     "myyuv_gpu_dct_crop", "myyuv_gpu_dct_crop_device", "myyuv_gpu_dct_join", "myyuv_gpu_dct_join_device",
     "myyuv_metric_psnr", "myyuv_metric_ssim", "myyuv_gpu_iyuv_compare", "myyuv_gpu_iyuv_compare_device",
     "myyuv_gpu_dct_compare", "myyuv_gpu_dct_compare_device",
@@ -221,6 +226,9 @@ def load():
     L.myyuv_gpu_dct_transform.argtypes = [vp, u8p, u32, u32, u32, u8p, u32, u8p, u8p, u32, ctypes.POINTER(u32),
                                           i64p]
     L.myyuv_gpu_dct_transform_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, u32, u8p, vp, u32, vp, vp]
+    L.myyuv_gpu_dct_downscale.argtypes = [vp, u8p, u32, u32, u32, u8p, u32, u8p, u8p, u32, ctypes.POINTER(u32),
+                                          i64p]
+    L.myyuv_gpu_dct_downscale_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, u32, u8p, vp, u32, vp, vp]
     L.myyuv_gpu_dct_crop.argtypes = [vp, u8p, u32, u32, u32, u32, u32, u32, u32, u8p, u32, ctypes.POINTER(u32), i64p]
     L.myyuv_gpu_dct_crop_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u32, u32, u32, u32, vp, u32, vp, vp]
     L.myyuv_gpu_dct_join.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u32), u32, u32, u32, u32, u8p, u32,
@@ -852,6 +860,48 @@ class Codec:
         if rc:
             raise CodecError(rc)
 
+    # -- downscale: the DCT stream of the 1/2, 1/4 or 1/8-size frame from a DCT stream,
+    # the small frame never in memory (defined in include/myyuv_hip.h) --
+    def downscale(self, payload, w, h, q_src, denom, q_dst=None):
+        """DCTYUV payload of a w x h frame written at q_src -> the payload of
+        the (w/denom) x (h/denom) frame at q_dst (default: q_src), as bytes:
+        compress(decompress_scaled(payload, denom), q_dst), bit for bit."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        d = int(denom)
+        cap = payload_bound(int(w) // d, int(h) // d) if d in (2, 4, 8) else 0
+        out = np.empty(max(1, cap), np.uint8)
+        n = self.downscale_into(src, w, h, q_src, d, q_src if q_dst is None else q_dst, out)
+        return out[:n].tobytes()
+
+    def downscale_into(self, payload, w, h, q_src, denom, q_dst, out):
+        """downscale from / into the caller's C-contiguous uint8 arrays, which
+        must not overlap; returns the result's size.  `out` is sized by its
+        byte count (payload_bound(w/denom, h/denom) always fits; a short one
+        fails with E_CAPACITY, CodecError.need the size needed)."""
+        src = _u8_array(payload, "payload")
+        dst = _u8_array(out, "out", writable=True)
+        size = ctypes.c_uint32(0)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_downscale(self._h, _u8(src), src.nbytes, w, h, _u8(_q(q_src)), int(denom),
+                                            _u8(_q(q_dst)), _u8(dst), dst.nbytes, ctypes.byref(size),
+                                            ctypes.byref(bad))
+        if rc:
+            err = CodecError(rc, bad.value)
+            err.need = size.value
+            raise err
+        return size.value
+
+    def downscale_device(self, d_payload, d_sizes, cap_in, nframes, w, h, q_src, denom, q_dst, d_out, cap_out,
+                         d_out_sizes, stream=None):
+        """Device-resident batch, as requantize_device: stream f at d_payload +
+        f*cap_in -> the 1/denom-size stream f at d_out + f*cap_out, its size at
+        d_out_sizes[f]; asynchronous, errors through sync_status."""
+        rc = load().myyuv_gpu_dct_downscale_device(self._h, d_payload, d_sizes, cap_in, nframes, w, h,
+                                                   _u8(_q(q_src)), int(denom), _u8(_q(q_dst)), d_out, cap_out,
+                                                   d_out_sizes, stream)
+        if rc:
+            raise CodecError(rc)
+
     # -- crop and join: a rectangle cut out of a DCT stream, a grid of streams laid
     # side by side as one, on the chunk bytes (defined in include/myyuv_hip.h) --
     def crop(self, payload, w, h, region):
@@ -970,19 +1020,19 @@ class Codec:
         if kernels is None:
             rc = load().myyuv_hip_profile(self._h, 1 if enable else 0)
         else:
-            mask = sum(1 << KERNELS_EVERY.index(k) for k in kernels) if enable else 0
+            mask = sum(1 << KERNELS_FULL.index(k) for k in kernels) if enable else 0
             rc = load().myyuv_hip_profile_kernels(self._h, mask)
         if rc:
             raise CodecError(rc)
 
     def kernel_stats(self):
-        """{name: (summed ms, launches)} for every name of KERNELS_EVERY."""
-        ms = (ctypes.c_double * K_LIMIT)()
-        n = (ctypes.c_int64 * K_LIMIT)()
-        rc = load().myyuv_hip_kernel_stats_n(self._h, K_LIMIT, ms, n)
+        """{name: (summed ms, launches)} for every name of KERNELS_FULL."""
+        ms = (ctypes.c_double * K_BOUND)()
+        n = (ctypes.c_int64 * K_BOUND)()
+        rc = load().myyuv_hip_kernel_stats_n(self._h, K_BOUND, ms, n)
         if rc:
             raise CodecError(rc)
-        return {KERNELS_EVERY[i]: (ms[i], n[i]) for i in range(K_LIMIT)}
+        return {KERNELS_FULL[i]: (ms[i], n[i]) for i in range(K_BOUND)}
 
     def tinfo_guard(self, ntiles, arm):
         """Diagnostic (not in include/myyuv_hip.h): arm=True writes a canary
