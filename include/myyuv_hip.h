@@ -879,6 +879,46 @@ int myyuv_gpu_dct_compress_to_sse_device(myyuv_hip_handle h, const void* d_iyuv,
  * dB figure reject it (MYYUV_E_ARG). */
 uint64_t myyuv_metric_sse_for_psnr(double db, uint64_t nsamples);
 
+/* Compress from BMP: the DCT stream of a BMP pixel array in one pass, the way
+ * INTO a stream for pictures that arrive as BGR(A).  For `bmp_data`, `width`,
+ * `height` and `bit_count` as myyuv_gpu_bmp_to_iyuv takes them (signed header
+ * fields, BGR or BGRA as stored) the result is, byte for byte,
+ *   compress(bmp_to_iyuv(bmp_data, width, height, bit_count), |width|, |height|, quality)
+ * that is myyuv_gpu_dct_compress applied to myyuv_gpu_bmp_to_iyuv's output; no
+ * new arithmetic is defined.  One kernel (MYYUV_K_BMP_FDCT) converts a strip
+ * of pixels and transforms its blocks, so the IYUV frame exists nowhere: the
+ * device holds the pixels, the encoder's workspace (myyuv_hip_reserve /
+ * myyuv_hip_reserve_batch for |width| x |height|) and the stream.  The call
+ * runs that kernel and the split encoder's later kernels under every
+ * MYYUV_ENCODER.
+ * Checks and errors, in this order: the handle and the pointers
+ * (MYYUV_E_ARG); then what the chain's first failing call would return:
+ *   1. myyuv_gpu_bmp_to_iyuv's: MYYUV_E_BMP_INVALID (|width| % 4, bit_count
+ *      0), MYYUV_E_BMP_SIGN (a zero or doubly negative size),
+ *      MYYUV_E_BMP_UNSUPPORTED (odd height, not 24 / 32 bpp), MYYUV_E_ARG (more
+ *      than 4 GiB of BGRA);
+ *   2. myyuv_gpu_dct_compress's for (|width|, |height|, quality, cap):
+ *      MYYUV_E_QUALITY, then per plane (Y, U, V) MYYUV_E_WIDTH before
+ *      MYYUV_E_HEIGHT (so both must be multiples of 16; a frame beyond the
+ *      kernels' 32-bit offsets is MYYUV_E_ARG before them), and last, once the
+ *      size is known, MYYUV_E_CAPACITY with *payload_size set. */
+int myyuv_gpu_bmp_dct_compress(myyuv_hip_handle h, const uint8_t* bmp_data, int32_t width, int32_t height,
+                               uint16_t bit_count, const uint8_t quality[3], uint8_t* payload, uint32_t cap,
+                               uint32_t* payload_size);
+/* Device-resident batch: pixel array f at d_bmp_data + f*|width|*|height|*
+ * bit_count/8 -> payload f at d_payload + f*cap (cap a multiple of 4 when
+ * nframes > 1), its size at d_payload_sizes[f]; asynchronous on `stream` (NULL
+ * = the context's), no allocation once the workspace has grown.  d_bmp_data is
+ * 16-byte (32 bpp) or 4-byte (24 bpp) aligned, as myyuv_gpu_iyuv_to_bmp_device
+ * asks of its pixel array, and d_payload 4-byte aligned: a misaligned pointer,
+ * like nframes == 0, is MYYUV_E_ARG, after step 1's errors (the alignment
+ * depends on bit_count) and before step 2's.  A payload beyond `cap` is a
+ * device-side error (MYYUV_E_CAPACITY through myyuv_hip_sync_status), as in
+ * myyuv_gpu_dct_compress_batch_device. */
+int myyuv_gpu_bmp_dct_compress_device(myyuv_hip_handle h, const void* d_bmp_data, uint32_t nframes, int32_t width,
+                                      int32_t height, uint16_t bit_count, const uint8_t quality[3], void* d_payload,
+                                      uint32_t cap, uint32_t* d_payload_sizes, void* stream);
+
 /* Host-buffer batches (many frames per call; §7 step 9:
  * transfers overlapped with the kernels).  The batch runs in chunks of up to
  * 8 frames through two device slots: chunk k's host -> device copies, chunk
@@ -972,7 +1012,13 @@ int myyuv_hip_sync_status(myyuv_hip_handle h, void* stream, int64_t* bad_block);
  * with it too).  The downscaler's id follows it; MYYUV_K_BOUND is the bound of
  * all ids, and the length to pass to myyuv_hip_kernel_stats_n for all of them. */
 #define MYYUV_K_DOWNSCALE 23 /* decode + scaled inverse + forward transform of the downscaler (downscale) */
-#define MYYUV_K_BOUND 24     /* every id is below this */
+#define MYYUV_K_BOUND 24     /* every id above is below this */
+/* MYYUV_K_BOUND is frozen as the bounds before it (callers size their arrays
+ * with it too).  The id of compress-from-BMP follows it; MYYUV_K_TOP is the
+ * bound of all ids, and the length to pass to myyuv_hip_kernel_stats_n for all
+ * of them. */
+#define MYYUV_K_BMP_FDCT 24  /* BMP -> IYUV conversion + K1's forward transform of compress-from-BMP (bmp_fdct) */
+#define MYYUV_K_TOP 25       /* every id is below this */
 int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 /* As myyuv_hip_profile, but stamps only the kernels whose bit (1 << MYYUV_K_*)
  * is set in `mask` (0 disables): event stamping costs host and queue time per
@@ -980,8 +1026,8 @@ int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 int myyuv_hip_profile_kernels(myyuv_hip_handle h, uint32_t mask);
 int myyuv_hip_kernel_stats(myyuv_hip_handle h, double ms[MYYUV_K_COUNT],
                            int64_t launches[MYYUV_K_COUNT]);
-/* The same for the first min(n, MYYUV_K_BOUND) ids; entries from
- * MYYUV_K_BOUND on, if any, are set to 0. */
+/* The same for the first min(n, MYYUV_K_TOP) ids; entries from
+ * MYYUV_K_TOP on, if any, are set to 0. */
 int myyuv_hip_kernel_stats_n(myyuv_hip_handle h, uint32_t n, double* ms, int64_t* launches);
 
 /* Block-level entry points for known-answer tests (device round trip of one

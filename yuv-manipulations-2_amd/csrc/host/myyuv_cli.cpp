@@ -9,6 +9,9 @@
 // (main.cpp:100-136):
 //   myyuv_cli in.bmp -info
 //   myyuv_cli in.bmp -to_yuv IYUV -o out.myyuv   (conversion on the GPU, K7)
+// both steps at once (compress from BMP, include/myyuv_hip.h: the file
+// -to_yuv IYUV followed by -compress DCT writes, no IYUV frame in between):
+//   myyuv_cli in.bmp -compress DCT q [q [q]] -o out.myyuv
 // the way back, which the reference leaves to its viewers (K8; a compressed
 // input is decoded and converted on the device):
 //   myyuv_cli in.myyuv -to_bmp [24|32] [-chroma nearest|linear] -o out.bmp
@@ -110,6 +113,8 @@ void usage() {
             << "      (PSNR and 8x8-block SSIM per plane between two images of one size, compressed or not)\n"
             << "  myyuv_cli IMAGE.bmp -info\n"
             << "  myyuv_cli IMAGE.bmp -to_yuv IYUV -o OUT.myyuv\n"
+            << "  myyuv_cli IMAGE.bmp -compress DCT Q [Q [Q]] -o OUT.myyuv\n"
+            << "      (-to_yuv IYUV and -compress DCT in one pass on the GPU, the same file)\n"
             << "  myyuv_cli -batch-compress DCT Q [Q [Q]] [-devices D0,D1,...] -o OUTDIR IMAGE.myyuv...\n"
             << "  myyuv_cli -batch-decompress -o OUTDIR IMAGE.myyuv...\n"
             << "\nYUV formats:\nIYUV\n\nCompression formats for YUV:\nDCT\n"
@@ -657,6 +662,28 @@ int run_bmp(const myyuv::BMP& bmp, size_t a, const std::vector<std::string>& arg
     const float ms = elapsed_ms([&] { out = myyuv::YUV(bmp, myyuv::YUV::FourccFormats::IYUV); });
     std::cout << "BMP to YUV (" << args[a + 1] << ") : " << ms << " ms\n";
     out.dump(args[a + 3]);
+    return 0;
+  }
+  if (cmd == "-compress") {  // DCT Q [Q [Q]] -o OUT.myyuv: -to_yuv IYUV and -compress DCT in one GPU pass
+    size_t k = a + 1;
+    const bool dct = k < args.size() && args[k] == "DCT";
+    std::vector<std::string> params;
+    for (k++; dct && k < args.size() && args[k] != "-o"; k++) params.push_back(args[k]);
+    if (!dct || args.size() != k + 2) {
+      std::cout << "Invalid argument, -compress must be followed by `DCT Q [Q [Q]] -o /path/to/new_image.myyuv`\n";
+      usage();
+      return 1;
+    }
+    std::string label = " ";
+    for (const auto& p : params) label += p + " ";
+    myyuv::YUV out;
+    const float ms = elapsed_ms([&] {
+      uint8_t q[3];
+      dct_qualities(params, q);
+      out = myyuvDCT::compress_DCT_planar(bmp, {q[0], q[1], q[2]});
+    });
+    std::cout << "BMP DCT compression (" << label << ") : " << ms << " ms\n";
+    out.dump(args[k + 1]);
     return 0;
   }
   std::cout << "Invalid command " << cmd << '\n';

@@ -562,6 +562,35 @@ myyuv::YUV compress_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 
   return res;
 }
 
+// The same from BMP pixels in one GPU pass (myyuv_gpu_bmp_dct_compress): the
+// raw-image header as bmp_to_yuv_map[IYUV] sets it, then the rewrite above.
+myyuv::YUV compress_DCT_planar(const myyuv::BMP& bmp, const std::array<uint8_t, 3>& params) {
+  using myyuv::YUV;
+  if (!bmp.isValid()) throw std::runtime_error("BMP is invalid");
+  for (uint8_t q : params)
+    if (q < 1 || q > 100) throw std::runtime_error("Level of quality must be between 1 and 100");
+  const uint32_t w = bmp.trueWidth(), h = bmp.trueHeight();
+  std::vector<uint8_t> payload(myyuv_dct_payload_bound(w, h));
+  uint32_t size = 0;
+  const int rc = myyuv_gpu_bmp_dct_compress(t_codec.get(), bmp.data, bmp.header.width, bmp.header.height,
+                                            bmp.header.bit_count, params.data(), payload.data(),
+                                            (uint32_t)payload.size(), &size);
+  if (rc) fail(rc);
+  YUV res;
+  res.header.fourcc_format = YUV::FourccFormats::IYUV;
+  res.header.width = w;
+  res.header.height = h;
+  res.header.compression = YUV::Compressions::DCT;
+  res.header.compression_params_size = 3;
+  res.header.compression_params_pos = sizeof(myyuv::YUVHeader);
+  res.header.data_pos = sizeof(myyuv::YUVHeader) + 3;
+  res.header.data_size = size;
+  res.compression_params = new uint8_t[3]{params[0], params[1], params[2]};
+  res.data = new uint8_t[size];
+  std::memcpy(res.data, payload.data(), size);
+  return res;
+}
+
 namespace {
 
 // Frames `idx` of `frames` (any geometries) on context h: frames of one

@@ -150,6 +150,12 @@ namespace myyuvDCT {
 // myyuv_DCT/DCT.hpp:16,25 — same signatures, HIP implementation.
 myyuv::YUV compress_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 3>& params);
 myyuv::YUV decompress_DCT_planar(const myyuv::YUV& yuv, const std::array<uint8_t, 3>& params);
+// Compress from BMP (include/myyuv_hip.h): the same YUV (header, params, data)
+// as compress_DCT_planar(YUV(bmp, IYUV), params), through
+// myyuv_gpu_bmp_dct_compress: the IYUV frame exists neither here nor on the
+// device.  YUV(bmp, IYUV)'s check and message for an invalid BMP, then
+// compress_DCT_planar's for the qualities.
+myyuv::YUV compress_DCT_planar(const myyuv::BMP& bmp, const std::array<uint8_t, 3>& params);
 // Region decode (include/myyuv_hip.h): the rw x rh frame cropped from the full
 // decode at (rx, ry), of which only the region's chunks are read.  The quality
 // bytes are the frame's compression parameters; the header is

@@ -14,6 +14,7 @@
 #include <utility>
 #include <vector>
 
+#include "bmp_fdct.h"
 #include "codec_common.hpp"
 #include "downscale.h"
 #include "k_chain.hpp"
@@ -95,6 +96,8 @@ template <int BPP>
 __global__ void k_bmp_to_iyuv(const uint8_t*, uint32_t, uint32_t, uint32_t, uint8_t*);
 template <int BPP, int LINEAR>
 __global__ void k_iyuv_to_bmp(const uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t*);
+template <int BPP>
+__global__ void k_bmp_fdct(const uint8_t*, myyuv_bmpfdct::Map, FrameGeom, const QTables*, uint4*, uint8_t*, uint32_t*);
 }  // namespace myyuv_gpu
 
 using namespace myyuv_gpu;
@@ -261,8 +264,8 @@ struct myyuv_hip_ctx {
   };
   uint32_t prof = 0;  // bit k: stamp kernel id k
   uint32_t skip = 0;  // diagnostic: bit k: do not launch kernel id k (myyuv_debug_skip_kernels)
-  double ms[MYYUV_K_BOUND] = {};
-  int64_t launches[MYYUV_K_BOUND] = {};
+  double ms[MYYUV_K_TOP] = {};
+  int64_t launches[MYYUV_K_TOP] = {};
   std::vector<Stamp> pending;
   std::vector<Event> free_events;
   // set once every piece of it exists (pipe_init)

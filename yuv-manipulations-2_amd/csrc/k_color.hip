@@ -17,6 +17,8 @@
 // plane.  colorData's re-orientation is folded into the source addressing
 // (no flipped copy of the image).
 //
+// The per-pixel arithmetic, the 4-pixel loads and the tile-row loop are in
+// color_px.hpp, shared with compress-from-BMP (k_transform.hip, k_bmp_fdct).
 // Numerics are the reference x86-64 build's (checked against it and against
 // the golden chef-with-trumpet.myyuv in tests/test_color.py): fp32
 // Y = 0.299 R + 0.587 G + 0.114 B, products and sums left to right, no FMA
@@ -30,46 +32,13 @@
 
 #include "codec_common.hpp"
 #include "color_div.hpp"
+#include "color_px.hpp"
 #include "k_metric.hpp"
 
 namespace myyuv_gpu {
 
-namespace {
-
-__device__ __forceinline__ uint32_t trunc_u8(float x) { return (uint32_t)(int32_t)x & 0xFFu; }
-
-// getYUV444FromRGB2x2's per-pixel step; returns Y and the two chroma values
-// already divided by 4 with round-to-nearest (divide_roundnearest(c, 4)).
-__device__ __forceinline__ void pixel(uint32_t b, uint32_t g, uint32_t r, uint32_t& y,
-                                      uint32_t& cb4, uint32_t& cr4) {
-  const float B = (float)b, G = (float)g, R = (float)r;
-  const float Y = 0.299f * R + 0.587f * G + 0.114f * B;
-  y = trunc_u8(Y);
-  cb4 = (((trunc_u8((B - Y) * 0.564f) + 128u) & 0xFFu) + 2u) >> 2;
-  cr4 = (((trunc_u8((R - Y) * 0.713f) + 128u) & 0xFFu) + 2u) >> 2;
-}
-
-// byte k of a little-endian word array (k static after unrolling)
-template <int N>
-__device__ __forceinline__ uint32_t byte_at(const uint32_t (&w)[N], int k) {
-  return (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu;
-}
-
-// Four consecutive source pixels starting at pixel index `pix` (pix % 4 == 0).
-template <int BPP>
-__device__ __forceinline__ void load4(const uint8_t* __restrict__ src, size_t pix,
-                                      uint32_t (&w)[BPP]) {
-  const uint32_t* p = reinterpret_cast<const uint32_t*>(src + pix * BPP);
-  if constexpr (BPP == 4) {
-    const uint4 v = *reinterpret_cast<const uint4*>(p);
-    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < BPP; i++) w[i] = p[i];
-  }
-}
-
-}  // namespace
+using px::load4;
+using px::tile_row;
 
 // One lane per 4x2 tile, grid-stride.  orient: 0 = rows as stored (width > 0,
 // height < 0), 1 = pixel order reversed (width < 0, height > 0), 2 = rows
@@ -99,20 +68,7 @@ __global__ __launch_bounds__(256) void k_bmp_to_iyuv(const uint8_t* __restrict__
         base = (size_t)(H - 1 - (r + dr)) * W + c;
       uint32_t w[BPP];
       load4<BPP>(src, base, w);
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        uint32_t b, g, rr;
-        if (orient == 1) {  // uniform branch: both orders keep static byte indices
-          b = byte_at(w, (3 - k) * BPP), g = byte_at(w, (3 - k) * BPP + 1), rr = byte_at(w, (3 - k) * BPP + 2);
-        } else {
-          b = byte_at(w, k * BPP), g = byte_at(w, k * BPP + 1), rr = byte_at(w, k * BPP + 2);
-        }
-        uint32_t y, cb4, cr4;
-        pixel(b, g, rr, y, cb4, cr4);
-        Y[dr] |= y << (8 * k);
-        cb[k >> 1] += cb4;
-        cr[k >> 1] += cr4;
-      }
+      tile_row<BPP>(w, orient == 1, Y[dr], cb, cr);
     }
     *reinterpret_cast<uint32_t*>(dst + (size_t)r * W + c) = Y[0];
     *reinterpret_cast<uint32_t*>(dst + (size_t)(r + 1) * W + c) = Y[1];

@@ -1,5 +1,6 @@
-// k_transform.hip — K1 fdct_quant and K6 dequant_idct for gfx950, and
-// k_coef_compare, K6's transform against a source frame (at the end).
+// k_transform.hip — K1 fdct_quant and K6 dequant_idct for gfx950,
+// k_coef_compare, K6's transform against a source frame, and k_bmp_fdct, K1's
+// transform fed from BMP pixels (at the end).
 //
 // Streaming kernels: K1 reads 1 B/sample (u8 pixel) and writes 2 B/sample
 // (int16 coefficient), K6 the reverse (3 B/sample each).  The
@@ -77,7 +78,9 @@
 // evaluations whose every operation rounds once to nearest.
 #include <stddef.h>
 
+#include "bmp_fdct.h"
 #include "codec_common.hpp"
+#include "color_px.hpp"
 #include "k1_store.hpp"
 #include "k_metric.hpp"
 #include "xform_common.hpp"
@@ -481,5 +484,109 @@ __global__ __launch_bounds__(256) void k_coef_compare(const uint4* __restrict__ 
   CompareRows out{G, src, part, map};
   dequant_idct_units(coef, rmask, zq, G, tile, sq, sink, out);
 }
+
+// ---- compress from BMP ------------------------------------------------------
+//
+// k_bmp_fdct<BPP>: K7's conversion and K1's transform in one launch, the IYUV
+// frame never in HBM (include/myyuv_hip.h, "Compress from BMP").  The work map
+// is bmp_fdct.h's: wave blockIdx.x of frame blockIdx.y owns a strip of 16 pixel
+// rows by up to 256 columns, up to 16 macroblocks.
+//  - Conversion: lane l converts the eight 4 x 2 tiles of the strip's tile
+//    column l (px::tile_row: K7's arithmetic), one 16-B (BGRA) or 12-B (BGR)
+//    load per tile row, a wave-instruction reading 1 KiB (768 B) of one pixel
+//    row; the loads of four tiles are issued before the first is converted, so
+//    HBM latency hides behind the wave's own arithmetic.  The luma dwords and
+//    chroma byte pairs go into the wave's image of block pictures (72-B slots:
+//    the stores and fdct_load's reads are bank-conflict-free, bmp_fdct.h).
+//  - Transform: up to four Y units, one U, one V unit of 16 slots, four lanes
+//    per block (fdct_core: K1's fast path and, on a failed proof, the exact path
+//    in the same wave, so there is no fix list).  Each unit's quads, row masks
+//    and info words go out as K1's do (store_block_rows_buf) at the block's
+//    index in the frame; slots past the strip's blocks are dropped by the
+//    descriptors' range (a narrow strip's unused slots hold pixel 128).
+// Every block of the frame belongs to exactly one wave, every source pixel is
+// read once, nothing depends on another wave, and there is no barrier.
+// (3 waves per SIMD: the wave's LDS, 13 KiB with the image, the transpose tile
+// and K1's tables, admits 12 workgroups per CU)
+#ifndef MYYUV_BMP_DEPTH
+// tiles whose loads are issued before the first is converted (1, 2, 4 or 8);
+// all 8 measured the same as 4 (8192x8192 BGRA: 157 against 159 us), for 3 more VGPRs
+#define MYYUV_BMP_DEPTH 4
+#endif
+template <int BPP>
+__global__ __launch_bounds__(64) void k_bmp_fdct(const uint8_t* __restrict__ src, myyuv_bmpfdct::Map M, FrameGeom G,
+                                                 const QTables* __restrict__ qt, uint4* __restrict__ coef,
+                                                 uint8_t* __restrict__ rmask, uint32_t* __restrict__ binfo) {
+  namespace bf = myyuv_bmpfdct;
+  static_assert(bf::kUnit == kXfUnit && bf::kSlotBytes % 8 == 0, "fdct_load's 8-B rows, K1's units");
+  static_assert(offsetof(QTables, r) == sizeof(float) * kSqR && offsetof(QTables, kb) == sizeof(float) * kSqKb,
+                "layout");
+  __shared__ uint2 simg[bf::kSlots * bf::kSlotBytes / 8];
+  __shared__ float tile[kXfUnit * kTile];
+  __shared__ float sqr[kSqWords];  // QTables::q, r, kb
+  __shared__ uint4 szz[8];
+  const uint32_t lane = threadIdx.x;
+  const bf::Strip S = bf::strip_of(M, blockIdx.x);
+  uint8_t* img = reinterpret_cast<uint8_t*>(simg);
+  stage_zz(szz);
+  for (uint32_t i = lane; i < (uint32_t)kSqWords; i += kWave) sqr[i] = qt->q[0][i];
+  if (S.nmb < 16u) {  // (wave-uniform) a narrow strip: its unused slots are transformed with the rest of their unit
+    for (uint32_t i = lane; i < bf::kSlots * bf::kSlotBytes / 8; i += kWave) simg[i] = make_uint2(0x80808080u, 0x80808080u);
+    wave_sync();
+  }
+
+  // ---- conversion: tile column `lane`, kDepth tiles' loads in flight at a time
+  constexpr uint32_t kDepth = MYYUV_BMP_DEPTH;
+  static_assert(bf::kTileRows % kDepth == 0, "whole batches");
+  if (lane < bf::live_lanes(S)) {
+    // the lane's first tile row; row r of the strip is r * step bytes further (wave-uniform)
+    const uint8_t* fr = src + (size_t)blockIdx.y * ((size_t)M.w * M.h * BPP) + (size_t)bf::tile_src(M, S, lane, 0, 0) * BPP;
+    const int64_t step = bf::row_step(M) * BPP;
+#pragma unroll
+    for (uint32_t t0 = 0; t0 < bf::kTileRows; t0 += kDepth) {
+      uint32_t w[kDepth][2][BPP];
+#pragma unroll
+      for (uint32_t i = 0; i < kDepth; i++)
+#pragma unroll
+        for (uint32_t dr = 0; dr < 2; dr++) px::load4<BPP>(fr + (int64_t)(2 * (t0 + i) + dr) * step, 0, w[i][dr]);
+#pragma unroll
+      for (uint32_t i = 0; i < kDepth; i++) {
+        const uint32_t ty = t0 + i;
+        uint32_t Y[2] = {0, 0}, cb[2] = {0, 0}, cr[2] = {0, 0};
+        px::tile_row<BPP>(w[i][0], M.orient == 1, Y[0], cb, cr);
+        px::tile_row<BPP>(w[i][1], M.orient == 1, Y[1], cb, cr);
+        *reinterpret_cast<uint32_t*>(img + bf::luma_byte(S, lane, ty, 0)) = Y[0];
+        *reinterpret_cast<uint32_t*>(img + bf::luma_byte(S, lane, ty, 1)) = Y[1];
+        uint8_t* uc = img + bf::chroma_byte(lane, ty);
+        *reinterpret_cast<uint16_t*>(uc) = (uint16_t)((cb[0] & 0xFFu) | (cb[1] & 0xFFu) << 8);
+        *reinterpret_cast<uint16_t*>(uc + (bf::kSlotV - bf::kSlotU) * bf::kSlotBytes) =
+            (uint16_t)((cr[0] & 0xFFu) | (cr[1] & 0xFFu) << 8);
+      }
+    }
+  }
+  wave_sync();  // the image is complete
+
+  // ---- K1's per-unit body on the strip's blocks, lane (b, q)
+  const uint32_t q = lane & 3u, b = lane >> 2;
+  float* tb = tile + b * kTile;
+  const K1Rsrc rs = k1_rsrc(coef, rmask, binfo, G);
+  const uint32_t nu = bf::units(S);
+#pragma unroll 1
+  for (uint32_t k = 0; k < nu; k++) {
+    const bf::UnitOf U = bf::unit_of(S, k);
+    const bool lv = b < U.nlive;
+    const uint32_t g = blockIdx.y * G.cum[3] + (U.p == 0 ? G.cum[0] : (U.p == 1 ? G.cum[1] : G.cum[2])) +
+                       bf::plane_block(M, S, U, lv ? b : 0u);
+    fdct_core(img + bf::kSlotBytes * (U.slot0 + b), tb, q, sqr, U.p, [&](const uint32_t (&c)[16], bool keep) {
+      store_block_rows_buf(c, q, lv && keep, g, rs, szz + 2 * q);
+    });
+    wave_sync();  // the next unit rewrites the tile
+  }
+}
+
+template __global__ void k_bmp_fdct<3>(const uint8_t*, myyuv_bmpfdct::Map, FrameGeom, const QTables*, uint4*, uint8_t*,
+                                       uint32_t*);
+template __global__ void k_bmp_fdct<4>(const uint8_t*, myyuv_bmpfdct::Map, FrameGeom, const QTables*, uint4*, uint8_t*,
+                                       uint32_t*);
 
 }  // namespace myyuv_gpu

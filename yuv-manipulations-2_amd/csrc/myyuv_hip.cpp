@@ -3,6 +3,7 @@
 // Host side of the gfx950 codec: frame geometry, quantisation tables, the
 // per-context workspace, and the launch sequences
 //   compress:   K1 fdct_quant -> K2 huff_encode (+ overflow pass) -> K4 stream_out
+//   from BMP:   bmp_fdct (K7's conversion + K1's FDCT) -> K2 (+ overflow pass) -> K4
 //   decompress: parse -> scan -> K5 huff_decode -> K6 dequant_idct
 //   region:     parse -> scan -> decode_region (a rectangle's blocks only)
 //   scaled:     parse -> scan -> decode_scaled (every block, at 1/2, 1/4 or 1/8 size)
@@ -1116,6 +1117,103 @@ int myyuv_gpu_dct_compress(myyuv_hip_handle c, const uint8_t* iyuv, uint32_t w, 
   if (size > cap) return MYYUV_E_CAPACITY;
   if (d2h(payload, c->payload.p, size, s)) return MYYUV_E_HIP;
   if (c->prof) drain_profile(c);
+  return 0;
+}
+
+// ---- compress from BMP (include/myyuv_hip.h) ----
+namespace {
+
+// G.nframes pixel arrays (array f at d_bmp + f * W * H * bits / 8) -> payload f
+// at d_out + f * cap.  k_bmp_fdct leaves K1's hand-off (quads, row masks, info
+// words) for every block of the batch; then the encoder from K2 on, as
+// launch_downscale runs it.  work[0] is zeroed here as K1 would have.  No IYUV
+// frame, no K7, no K1, no fix kernel (K1's fix lists and their parity are not
+// touched).  Workspace: reserve.
+int launch_bmp_compress(myyuv_hip_ctx* c, const FrameGeom& G, const void* d_bmp, uint32_t orient, uint16_t bits,
+                        void* d_out, uint32_t cap, uint32_t* d_size, hipStream_t s) {
+  const uint32_t nf = G.nframes;
+  const QTables* qt = c->qtd.as<const QTables>();
+  unsigned long long* err = c->err.as<unsigned long long>();
+  const myyuv_bmpfdct::Map M = myyuv_bmpfdct::make_map(G.pw[0], G.ph[0], orient);
+  int e = 0;
+  e |= hipMemsetAsync(c->work.p, 0, 4, s) != hipSuccess;
+  e |= launch(c, MYYUV_K_BMP_FDCT, bits == 32 ? k_bmp_fdct<4> : k_bmp_fdct<3>, dim3(M.nstrips, nf), dim3(kWave), s,
+              static_cast<const uint8_t*>(d_bmp), M, G, qt, c->coef.as<uint4>(), c->rmask.as<uint8_t>(),
+              c->binfo.as<uint32_t>());
+  e |= launch_huff_encode(c, G, s);
+  e |= launch(c, MYYUV_K_SCAN, k_tile_scan, dim3(nf), dim3(256), s, c->tinfo.as<uint32_t>(), G,
+              static_cast<uint8_t*>(d_out), cap, d_size, err);
+  const uint32_t W = k2_win(nf * G.tcum[3]);  // (K2's windows, as launch_compress)
+  e |= launch(c, MYYUV_K_COMPACT, k_stream_out, dim3(ceil_div(G.tcum[3] * nf, 8 * W) * 8 * W), dim3(256), s,
+              c->stage.as<const uint32_t>(), c->tinfo.as<const uint32_t>(), c->sizes.as<const uint8_t>(),
+              c->srcoff.as<const uint32_t>(), c->oslots.as<const uint32_t>(), G, static_cast<uint8_t*>(d_out), cap,
+              W);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+}  // namespace
+
+int myyuv_gpu_bmp_dct_compress(myyuv_hip_handle c, const uint8_t* bmp_data, int32_t width, int32_t height,
+                               uint16_t bit_count, const uint8_t q[3], uint8_t* payload, uint32_t cap,
+                               uint32_t* payload_size) {
+  if (!c || !bmp_data || !payload || !payload_size || !q) return MYYUV_E_ARG;
+  uint32_t w = 0, h = 0, orient = 0;
+  FrameGeom G;
+  int e = bmp_check(width, height, bit_count, &w, &h, &orient);
+  if (e || (e = check_q(q)) || (e = make_geom(w, h, G))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const size_t in_bytes = (size_t)w * h * (bit_count / 8);
+  const uint32_t bound = myyuv_dct_payload_bound(w, h);
+  if ((e = reserve(c, G)) || (e = set_qtables(c, q, s))) return e;
+  if (c->bmp.grow(in_bytes) || c->payload.grow(bound)) return MYYUV_E_HIP;
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (h2d(c->bmp.p, bmp_data, in_bytes, s)) return MYYUV_E_HIP;
+  if ((e = launch_bmp_compress(c, G, c->bmp.p, orient, bit_count, c->payload.p, bound, c->psize.as<uint32_t>(), s)))
+    return e;
+  uint32_t size = 0;
+  if (hipMemcpyAsync(&size, c->psize.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return MYYUV_E_HIP;
+  int64_t bad = -1;
+  if ((e = read_err(c, s, &bad))) {
+    (void)reset_err(c, s);
+    return e;
+  }
+  *payload_size = size;
+  if (size > cap) return MYYUV_E_CAPACITY;
+  if (d2h(payload, c->payload.p, size, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+int myyuv_gpu_bmp_dct_compress_device(myyuv_hip_handle c, const void* d_bmp, uint32_t nframes, int32_t width,
+                                      int32_t height, uint16_t bit_count, const uint8_t q[3], void* d_payload,
+                                      uint32_t cap, uint32_t* d_sizes, void* stream) {
+  if (!c || !d_bmp || !d_payload || !d_sizes || !q) return MYYUV_E_ARG;
+  uint32_t w = 0, h = 0, orient = 0;
+  int e = bmp_check(width, height, bit_count, &w, &h, &orient);
+  if (e) return e;
+  // the kernel's 16-B / dword pixel loads; the stream writer's dword stores
+  if (nframes == 0 || ((uintptr_t)d_bmp & (bit_count == 32 ? 15 : 3)) || ((uintptr_t)d_payload & 3) ||
+      (nframes > 1 && (cap & 3)))
+    return MYYUV_E_ARG;
+  FrameGeom G;
+  if ((e = check_q(q)) || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes))) return e;
+  Entry en(c, stream);
+  // (as several launches when the batch's coefficient image would reach 4 GiB)
+  const uint32_t per = launch_frames(G, c->launch_blocks);
+  FrameGeom GL = G;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve(c, GL)) || (e = set_qtables(c, q, en.s))) return e;
+  const size_t in_bytes = (size_t)w * h * (bit_count / 8);
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GL.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
+    const uint8_t* px = static_cast<const uint8_t*>(d_bmp) + (size_t)f0 * in_bytes;
+    uint8_t* pay = static_cast<uint8_t*>(d_payload) + (size_t)f0 * cap;
+    if ((e = launch_bmp_compress(c, GL, px, orient, bit_count, pay, cap, d_sizes + f0, en.s))) return e;
+  }
   return 0;
 }
 
@@ -2611,7 +2709,7 @@ int myyuv_gpu_dct_decompress_to_bmp_frames(myyuv_hip_handle c, const uint8_t* co
 }
 
 int myyuv_hip_profile(myyuv_hip_handle c, int enable) {
-  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_BOUND) - 1u : 0u);
+  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_TOP) - 1u : 0u);
 }
 
 int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
@@ -2620,8 +2718,8 @@ int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
   DeviceGuard g(c->device);
   (void)hipStreamSynchronize(c->stream);
   drain_profile(c);
-  c->prof = mask & ((1u << MYYUV_K_BOUND) - 1u);
-  for (int k = 0; k < MYYUV_K_BOUND; k++) {
+  c->prof = mask & ((1u << MYYUV_K_TOP) - 1u);
+  for (int k = 0; k < MYYUV_K_TOP; k++) {
     c->ms[k] = 0;
     c->launches[k] = 0;
   }
@@ -2634,8 +2732,8 @@ int myyuv_hip_kernel_stats_n(myyuv_hip_handle c, uint32_t n, double* ms, int64_t
   DeviceGuard g(c->device);
   drain_profile(c);
   for (uint32_t k = 0; k < n; k++) {
-    ms[k] = k < MYYUV_K_BOUND ? c->ms[k] : 0.0;
-    launches[k] = k < MYYUV_K_BOUND ? c->launches[k] : 0;
+    ms[k] = k < MYYUV_K_TOP ? c->ms[k] : 0.0;
+    launches[k] = k < MYYUV_K_TOP ? c->launches[k] : 0;
   }
   return 0;
 }

@@ -41,10 +41,14 @@ KERNELS_EVERY = KERNELS_ALL + ["coef_compare", "probe_out"]
 K_COEF_CMP = KERNELS_EVERY.index("coef_compare")
 K_PROBE_OUT = KERNELS_EVERY.index("probe_out")
 K_LIMIT = len(KERNELS_EVERY)  # MYYUV_K_LIMIT: frozen like the bounds before it; the ids after it end at K_BOUND
-# the downscaler's id follows; Codec.profile / Codec.kernel_stats take and return KERNELS_FULL's names
+# the downscaler's id follows
 KERNELS_FULL = KERNELS_EVERY + ["downscale"]
 K_DOWNSCALE = KERNELS_FULL.index("downscale")
-K_BOUND = len(KERNELS_FULL)  # MYYUV_K_BOUND
+K_BOUND = len(KERNELS_FULL)  # MYYUV_K_BOUND: frozen like the bounds before it; the ids after it end at K_TOP
+# compress-from-BMP's id follows; Codec.profile / Codec.kernel_stats take and return KERNELS_TOP's names
+KERNELS_TOP = KERNELS_FULL + ["bmp_fdct"]
+K_BMP_FDCT = KERNELS_TOP.index("bmp_fdct")
+K_TOP = len(KERNELS_TOP)  # MYYUV_K_TOP
 E_TARGET = 18  # MYYUV_E_TARGET: "target not reachable" (error_message; strerror's table ends at 17)
 PROBE_SIZE, PROBE_METRIC = 1, 2  # MYYUV_PROBE_*
 # myyuv_block_metric, as the maps of the compare calls come back
@@ -85,6 +89,7 @@ EXPORTS = [
     "myyuv_gpu_dct_probe", "myyuv_gpu_dct_probe_device", "myyuv_metric_sse_for_psnr", "myyuv_hip_error_message",
     "myyuv_gpu_dct_compress_to_size", "myyuv_gpu_dct_compress_to_sse",
     "myyuv_gpu_dct_compress_to_size_device", "myyuv_gpu_dct_compress_to_sse_device",
+    "myyuv_gpu_bmp_dct_compress", "myyuv_gpu_bmp_dct_compress_device",
 ]
 
 
@@ -253,6 +258,8 @@ def load():
     L.myyuv_gpu_dct_compress_to_sse.argtypes = [vp, u8p, u32, u32, u64p, u8p, u32, ctypes.POINTER(u32), trp]
     L.myyuv_gpu_dct_compress_to_size_device.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp, trp, vp]
     L.myyuv_gpu_dct_compress_to_sse_device.argtypes = [vp, vp, u32, u32, u64p, vp, u32, vp, trp, vp]
+    L.myyuv_gpu_bmp_dct_compress.argtypes = [vp, u8p, i32, i32, u16, u8p, u8p, u32, ctypes.POINTER(u32)]
+    L.myyuv_gpu_bmp_dct_compress_device.argtypes = [vp, vp, u32, i32, i32, u16, u8p, vp, u32, vp, vp]
     L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -500,6 +507,45 @@ class Codec:
     def bmp_to_iyuv_device(self, d_bmp, width, height, bit_count, d_iyuv, stream=None):
         rc = load().myyuv_gpu_bmp_to_iyuv_device(self._h, d_bmp, int(width), int(height),
                                                  int(bit_count), d_iyuv, stream)
+        if rc:
+            raise CodecError(rc)
+
+    # -- compress from BMP: the DCT stream of a BMP pixel array in one pass, no
+    # IYUV frame in between (defined in include/myyuv_hip.h) --
+    def compress_bmp(self, bmp_data, width, height, bit_count, q):
+        """BMP::data (as stored; signed header width / height) -> DCTYUV
+        payload bytes: compress(bmp_to_iyuv(...), |width|, |height|, q), bit for
+        bit."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(bmp_data).cast("B"), np.uint8))
+        cap = payload_bound(abs(int(width)), abs(int(height)))
+        out = np.empty(max(1, cap), np.uint8)
+        n = self.compress_bmp_into(src, width, height, bit_count, q, out)
+        return out[:n].tobytes()
+
+    def compress_bmp_into(self, bmp_data, width, height, bit_count, q, out):
+        """compress_bmp from / into the caller's C-contiguous uint8 arrays;
+        returns the payload size.  `out` is sized by its byte count
+        (payload_bound(|width|, |height|) always fits; a short one fails with
+        E_CAPACITY, CodecError.need the size needed)."""
+        src = _u8_array(bmp_data, "bmp_data")
+        dst = _u8_array(out, "out", writable=True)
+        if src.nbytes < abs(int(width)) * abs(int(height)) * (int(bit_count) // 8):
+            raise ValueError("pixel array smaller than |w|*|h|*bit_count/8")
+        size = ctypes.c_uint32(0)
+        rc = load().myyuv_gpu_bmp_dct_compress(self._h, _u8(src), int(width), int(height), int(bit_count),
+                                               _u8(_q(q)), _u8(dst), dst.nbytes, ctypes.byref(size))
+        if rc:
+            err = CodecError(rc)
+            err.need = size.value
+            raise err
+        return size.value
+
+    def compress_bmp_device(self, d_bmp, nframes, width, height, bit_count, q, d_payload, cap, d_sizes, stream=None):
+        """Device-resident batch: pixel array f at d_bmp + f*|w|*|h|*bit_count/8
+        -> payload f at d_payload + f*cap, its size at d_sizes[f];
+        asynchronous, device-side errors through sync_status."""
+        rc = load().myyuv_gpu_bmp_dct_compress_device(self._h, d_bmp, int(nframes), int(width), int(height),
+                                                      int(bit_count), _u8(_q(q)), d_payload, cap, d_sizes, stream)
         if rc:
             raise CodecError(rc)
 
@@ -1020,19 +1066,19 @@ class Codec:
         if kernels is None:
             rc = load().myyuv_hip_profile(self._h, 1 if enable else 0)
         else:
-            mask = sum(1 << KERNELS_FULL.index(k) for k in kernels) if enable else 0
+            mask = sum(1 << KERNELS_TOP.index(k) for k in kernels) if enable else 0
             rc = load().myyuv_hip_profile_kernels(self._h, mask)
         if rc:
             raise CodecError(rc)
 
     def kernel_stats(self):
-        """{name: (summed ms, launches)} for every name of KERNELS_FULL."""
-        ms = (ctypes.c_double * K_BOUND)()
-        n = (ctypes.c_int64 * K_BOUND)()
-        rc = load().myyuv_hip_kernel_stats_n(self._h, K_BOUND, ms, n)
+        """{name: (summed ms, launches)} for every name of KERNELS_TOP."""
+        ms = (ctypes.c_double * K_TOP)()
+        n = (ctypes.c_int64 * K_TOP)()
+        rc = load().myyuv_hip_kernel_stats_n(self._h, K_TOP, ms, n)
         if rc:
             raise CodecError(rc)
-        return {KERNELS_FULL[i]: (ms[i], n[i]) for i in range(K_BOUND)}
+        return {KERNELS_TOP[i]: (ms[i], n[i]) for i in range(K_TOP)}
 
     def tinfo_guard(self, ntiles, arm):
         """Diagnostic (not in include/myyuv_hip.h): arm=True writes a canary
