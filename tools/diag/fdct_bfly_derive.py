@@ -39,6 +39,19 @@ kappa=g(5)*nI*(dI+e1)+nI*e1+delta*dI+g(8)*dI*dI*(2+g(8))
 ymax=nI*(dI+e1)*(1+g(5))   # |Y_f| <= ymax * A
 K=(kappa*(1+2**-20)+ymax*2**-21)*(1+2**-18)
 print("nI",nI,"dI",dI,"delta",delta,"kappa",kappa,"kappa/u",kappa/u,"K",K, "K/u", K/u)
+# the zero-row rule's constant (fdct_bfly.h "Zero rows"), in exact rationals:
+# kZeroRowK >= (max|N| / kBflyK) (1 + u)^6 / (1 - u)^7 (1 + 4 u); the header's
+# value is that minimum times (1 + 2^-20), rounded to float
+from fractions import Fraction as Fr
+hdr=open(os.path.join(ROOT, 'yuv-manipulations-2_amd', 'csrc', 'fdct_bfly.h')).read()
+kbfly=Fr(float(f32(float(re.search(r'kBflyK = ([-0-9.e]+)f', hdr).group(1)))))
+kzero=Fr(float(f32(float(re.findall(r'kZeroRowK = ([-0-9.e]+)f', hdr)[-1]))))
+uu=Fr(1,2**24)
+kmin=Fr(float(np.abs(N).max()))/kbfly*(1+uu)**6/(1-uu)**7*(1+4*uu)
+kz=f32(float(kmin*(1+Fr(1,2**20))))
+print("zero rows: max|N|/kBflyK",float(Fr(nI)/kbfly),"minimum K",float(kmin),"kZeroRowK",repr(float(kz)),float(kz).hex(),
+      "header",float(kzero),"margin",float(kzero/kmin-1))
+assert kzero>=kmin
 def lit(x): return repr(float(f32(x)))+'f'
 print("c0",lit(c0),"c4",lit(c4),"a2",lit(a2),"b2",lit(b2),"a6",lit(a6),"b6",lit(b6))
 for i in (1,3,5,7): print(i,[lit(N[i][j]) for j in range(4)])

@@ -33,8 +33,43 @@
 // (1 + 2^-20) covers the float evaluation of A * kb.  An output whose t is
 // further than beta from every half-integer rounds (half-even, magic add) to
 // the reference's roundf of fl(Y_ref / Q): fl(Y_ref / Q) lies strictly inside
-// the same (n - 1/2, n + 1/2).  A unit with any closer output goes to the
+// the same (n - 1/2, n + 1/2).  A block with any closer output goes to the
 // reference-order transform (k_fdct_fix).
+//
+// Zero rows.  Stage 2 works row by row (Y[i][.] depends on T[i][.] only), and
+// a row of T that is small enough quantises to eight zeros whatever its
+// shape; bfly_zero_row() decides that from S = sum_k |T[i][k]| before the row
+// is transformed, and a wave whose 16 blocks all pass it for rows 4..7 leaves
+// those rows' stage 2 out (fdct_fast: lane q owns rows q and q + 4, so rows
+// 4..7 are one half of every lane's work).  The rule, for row i of a block:
+//     fl(kb[i] * fma(S_f, kZeroRowK, A)) < 0.5,
+// S_f the float sum of the eight |T[i][k]| (7 adds).  It implies the proof
+// above for that row, with every output 0:
+//   - each y[v] of bfly_rows is a sum of products of its inputs with entries
+//     of N, and a rounding only scales a partial result by (1 + d), |d| <= u,
+//     so |y_f[v]| <= max|N| (1 + u)^5 S (5 roundings at most, S the exact sum;
+//     max|N| = kO1[0]: |y0| <= kC0 S, |y2|, |y6| <= kA2 S, the odd rows
+//     max|o| * sum |d_j| <= kO1[0] S);
+//   - S <= S_f / (1 - u)^7, and t = fl(y_f * fl(1/Q)) with fl(1/Q) <= r_max,
+//     so max_v |t| <= B := max|N| r_max S_f (1 + u)^6 / (1 - u)^7 (a product
+//     that underflows is below 2^-126 and passes everything below by itself:
+//     A kb <= 8192 * 7.95e-7);
+//   - kb[i] >= kBflyK r_max (bfly_row_bounds), so with kZeroRowK >= (max|N| /
+//     kBflyK) (1 + u)^6 / (1 - u)^7 (1 + 4 u) the rule's exact value
+//     kb (S_f kZeroRowK + A) is >= (A kb + B) + 4 u B, and its two roundings
+//     (the fma, the product) lower it by less than 2 u of itself: a float
+//     result < 0.5 means A kb + B + 4 u B < 0.5 (1 + 2.01 u), where B > 0.49
+//     whenever A kb + B > 0.49 + 0.0066, hence A kb + B < 0.5 (1 - 1.9 u);
+//   - then |t| <= B < 0.5, so every magic add of the row gives 0 and e = t,
+//     and the existing decision value fma(A, kb[i], max |e|) <= fl(A kb + B)
+//     (fma is monotone in its addend and rounds once) <= 0.5 - 2^-25 < 0.5.
+// So a row the rule passes is a row the existing proof passes, with zero
+// coefficients: what K1 stores and what it lists does not depend on whether a
+// wave took the skip, and bfly_block below stays the reference for both.
+// kZeroRowK is that minimum times (1 + 2^-20) (fdct_bfly_derive.py prints both;
+// the rule could pass ~1e-6 more rows at most).  tools/diag/
+// fdct_zero_rows_check.cpp (tests/test_fdct_zero_rows.py) checks the
+// implication block by block against bfly_block and the reference transform.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -47,8 +82,9 @@
 // MYYUV_BFLY_MUTANT (host check only, tests/test_fdct_edges.py): a deliberately
 // wrong build of the arithmetic below, to show that the test inputs tell it
 // from the real one.  1: the FMA chains as separate multiplies and adds; 2:
-// kC4 replaced by kC0 (one ulp of the constant).  Off (0) in every other
-// build; never in device code.
+// kC4 replaced by kC0 (one ulp of the constant); 3: kZeroRowK halved (the
+// zero-row rule passes rows that are not zero, tests/test_fdct_zero_rows.py).
+// Off (0) in every other build; never in device code.
 #ifndef MYYUV_BFLY_MUTANT
 #define MYYUV_BFLY_MUTANT 0
 #endif
@@ -79,6 +115,11 @@ constexpr float kO3[4] = {0.41573482751846313f, -0.0975450873374939f, -0.4903926
 constexpr float kO5[4] = {0.2777852416038513f, -0.49039262533187866f, 0.09754514694213867f, 0.41573476791381836f};
 constexpr float kO7[4] = {0.09754543751478195f, -0.2777852416038513f, 0.4157347083091736f, -0.49039262533187866f};
 constexpr float kBflyK = 7.946e-7f;
+#if MYYUV_BFLY_MUTANT == 3
+constexpr float kZeroRowK = 0.5f * 617157.8125f;
+#else
+constexpr float kZeroRowK = 617157.8125f;  // 0x1.2d58bap+19 (the header's "Zero rows")
+#endif
 
 MYYUV_BF_HD float odd4(const float (&o)[4], float d0, float d1, float d2, float d3) {
   return MYYUV_BF_FMA(o[3], d3, MYYUV_BF_FMA(o[2], d2, MYYUV_BF_FMA(o[1], d1, o[0] * d0)));
@@ -124,6 +165,30 @@ MYYUV_BF_HD void bfly_row_bounds(const float* r, float* kb) {
     kb[i] = (float)((double)kBflyK * m * (1.0 + 0x1p-20) * (1.0 + 0x1p-22));
   }
 }
+
+// The zero-row rule for one row of T (x[k] = T[i][k], a = the block's A as a
+// float, kb = kb[i]): the decision value, and whether the row's eight
+// coefficients are proven zero (the header's "Zero rows").  The kernel and
+// the host checks run these same operations.
+MYYUV_BF_HD float bfly_zero_row_dec(const float (&x)[8], float a, float kb) {
+  const float s = ((fabsf(x[0]) + fabsf(x[1])) + (fabsf(x[2]) + fabsf(x[3]))) +
+                  ((fabsf(x[4]) + fabsf(x[5])) + (fabsf(x[6]) + fabsf(x[7])));
+  return kb * fmaf(s, kZeroRowK, a);
+}
+MYYUV_BF_HD bool bfly_zero_row(const float (&x)[8], float a, float kb) { return bfly_zero_row_dec(x, a, kb) < 0.5f; }
+
+// Whether a plane's units are tested at all (kb4 = the plane's kb[4], a
+// function of its table: kBflyK / the smallest Q of row 4, the row of 4..7 with
+// the smallest entries in the quality tables).  With small quantisers hardly
+// any unit passes and the test only costs: on a noisy 3968x2944 photo at q90
+// (luma: row 4's smallest Q = 4, no unit of 11,408 passes; chroma: 20, 28-40 %
+// pass) K1 ran 1.0 % slower than without the test, the parent's own spread
+// being 0.2 % (profiles/r10a_zero_rows_ab.txt); at q75 (luma 9: 10 % pass,
+// chroma 50: 56-77 %) the planes together gain.  The gate lies between: planes
+// whose row 4 has an entry below 6 are not tested (luma from q ~ 84 up, chroma
+// from q 98).  Output does not depend on it.
+constexpr float kZeroRowGate = kBflyK / 5.5f;
+MYYUV_BF_HD bool bfly_zero_rows_tested(float kb4) { return kb4 < kZeroRowGate; }
 
 #if !defined(__HIPCC__)
 // The kernel's arithmetic for one whole block (host check): coefficients in
@@ -172,6 +237,26 @@ static inline int bfly_block(const unsigned char* px, const float* R, const floa
   }
   if (d) d->a = af;
   return ok;
+}
+// The block's votes in fdct_fast: bit i - 4 set when row i (4..7) passes the
+// zero-row rule; dec (may be null): the four decision values.  A wave skips
+// the rows' stage 2 when all of its storing blocks return 15.
+static inline int bfly_block_zero_rows(const unsigned char* px, const float* kb, float* dec = nullptr) {
+  unsigned a = 0;
+  for (int i = 0; i < 64; i++) a += px[i] > 128 ? px[i] - 128u : 128u - px[i];
+  float T[8][8];
+  for (int k = 0; k < 8; k++) {
+    float p[8], t[8];
+    for (int m = 0; m < 8; m++) p[m] = (float)px[m * 8 + k];
+    bfly_cols(p, t);
+    for (int i = 0; i < 8; i++) T[i][k] = t[i];
+  }
+  int votes = 0;
+  for (int i = 4; i < 8; i++) {
+    if (dec) dec[i - 4] = bfly_zero_row_dec(T[i], (float)a, kb[i]);
+    if (bfly_zero_row(T[i], (float)a, kb[i])) votes |= 1 << (i - 4);
+  }
+  return votes;
 }
 #endif
 

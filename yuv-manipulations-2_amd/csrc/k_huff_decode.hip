@@ -1666,8 +1666,8 @@ __global__ __launch_bounds__(64, 4) void k_downscale(const uint8_t* __restrict__
     const uint32_t slot = u0 + b;  // (< kImgBlocks: nout <= 64 / denom)
     const bool lv = slot < W.nout;
     const uint32_t g = g0 + myyuv_downscale::out_block(W, slot);
-    xf::fdct_core(img + 64u * slot, tb, q, sqr, p, [&](const uint32_t (&c)[16], bool keep) {
-      xf::store_block_rows_buf(c, q, lv && keep, g, rs, szz + 2 * q);
+    xf::fdct_core(img + 64u * slot, tb, q, lv, sqr, p, [&](const uint32_t (&c)[16], bool keep, auto hz) {
+      xf::store_block_rows_buf<decltype(hz)::value>(c, q, lv && keep, g, rs, szz);
     });
     xf::wave_sync();  // the next unit rewrites the tile
   }

@@ -30,12 +30,16 @@
 // planes, so the tables are uniform per unit) per wave.  Lane (b, q),
 // q = lane & 3:
 //   stage 1 owns columns 2q, 2q+1 (T[i][2q], T[i][2q+1] for i = 0..7),
-//   stage 2 owns rows 2q, 2q+1    (Y[2q][v], Y[2q+1][v] for v = 0..7),
+//   stage 2 owns rows 2q, 2q+1    (Y[2q][v], Y[2q+1][v] for v = 0..7) in K6,
+//           and rows q, q+4       (Y[q][v], Y[q+4][v]) in K1, so that rows
+//           4..7 of all 16 blocks are one half of every lane's stage 2 and
+//           the wave can leave it out together (zero rows, below),
 // and the 8x8 transposes (pixel rows -> columns, stage 1 -> stage 2) go
-// through a per-wave LDS tile (tix()).  Lane (b, q) loads / stores the
-// block's pixel rows 2q, 2q+1 directly (8 B each; 16 blocks x 8 B = 128 B
-// runs per row) and its two coefficient quads 2q, 2q+1 (codec_common.hpp
-// layout; 256 B runs).  The per-quality tables (QTables) are a device buffer.
+// through a per-wave LDS tile (tix(); K1's second one tixf()).  Lane (b, q)
+// loads / stores the block's pixel rows 2q, 2q+1 directly (8 B each; 16
+// blocks x 8 B = 128 B runs per row); K6 loads the coefficient quads 2q,
+// 2q+1, K1 stores the quads q, q+4 (codec_common.hpp layout; 256 B runs
+// either way).  The per-quality tables (QTables) are a device buffer.
 // A launch covers a batch of frames (FrameGeom::nframes): the waves stride
 // over the units of all of them, frame f's unit u being f * ucum[3] + u.
 //
@@ -47,13 +51,23 @@
 // block, |Y_fast - Y_ref| <= kappa * A (Higham gamma_k bounds on both
 // evaluations plus max|N - D|; fdct_bfly.h), and a row whose every
 // t = Y_fast * fl(1/Q) stays further than A * kb[row] from a half-integer
-// quantises to the reference's roundf(fl(Y_ref / Q)).  A unit where any row
-// fails is listed and recomputed by k_fdct_fix in the reference's order: the
+// quantises to the reference's roundf(fl(Y_ref / Q)).  A BLOCK where any row
+// fails is listed (the proof is per block: A and the row factors are the
+// block's own) and recomputed by k_fdct_fix in the reference's order: the
 // straight k-ascending sums of fp32-rounded products (DCT.cpp:232-266),
 // -ffp-contract=off (fdct_exact; its only fma is the near-tie test below).
+// Zero rows: before stage 2, S = sum_k |T[i][k]| bounds every output of row
+// i, and fl(kb[i] * fma(S, kZeroRowK, A)) < 0.5 implies both that all eight
+// t of the row round to 0 and that the row's proof above passes (fdct_bfly.h,
+// "Zero rows").  When every storing lane of a wave finds that for its row
+// q + 4, the wave skips stage 2, the quantisation, the packing, the info
+// word's counts and the store of rows 4..7: the bytes K1 writes and the blocks
+// it lists are those of the full path, whichever way a wave went.
 // tools/diag/fdct_bfly_check.cpp (tests/test_numerics.py) replays the fast
-// arithmetic on the host and checks every proven unit equals the reference.
-// K6 keeps the reference's order throughout.
+// arithmetic on the host and checks every proven block equals the reference;
+// tools/diag/fdct_zero_rows_check.cpp (tests/test_fdct_zero_rows.py) checks
+// that the zero-row rule implies the proof.  K6 keeps the reference's order
+// throughout.
 //   exact path /Q + roundf: t = y * fl(1/Q) is within |t| * 1.5 * 2^-23 of fl(y/Q)
 //     (two roundings of relative error 2^-24 plus fl(y/Q)'s own), so
 //     roundf(fl(y/Q)) == rint(t) unless a half-integer lies within
@@ -162,19 +176,20 @@ __global__ __launch_bounds__(256) MYYUV_K1_ATTR void k_fdct_quant(const uint8_t*
 
     // stores of lanes past the plane's end, and of blocks left to the exact
     // path, go to the sink (no branch: see load_rows)
-    auto store = [&](const uint32_t (&c)[16], bool keep) {
+    auto store = [&](const uint32_t (&c)[16], bool keep, auto hz) {
+      constexpr bool kHz = decltype(hz)::value;  // rows 4..7 of the unit are zero
       const bool lv = live && keep;
 #if MYYUV_K1_BUF
-      store_block_rows_buf(c, q, lv, g, rs, szz + 2 * q);
+      store_block_rows_buf<kHz>(c, q, lv, g, rs, szz);
 #else
-      uint4* dlo = lv ? coef + coef_quad(g, 2 * q) : sink + lane;
-      uint4* dhi = lv ? coef + coef_quad(g, 2 * q + 1) : sink + 64 + lane;
-      store_block_rows(c, q, lane, lv, g, dlo, dhi, rmask, binfo, szz + 2 * q, sink);
+      uint4* dlo = lv ? coef + coef_quad(g, q) : sink + lane;
+      uint4* dhi = lv ? coef + coef_quad(g, q + 4) : sink + 64 + lane;
+      store_block_rows<kHz>(c, q, lane, lv, g, dlo, dhi, rmask, binfo, szz, sink);
 #endif
     };
     uint32_t xr[4];
     fdct_load(img, q, xr);
-    const uint64_t bad = fdct_fast<true>(xr, tb, q, sqr, U.p, store);
+    const uint64_t bad = fdct_fast<true>(xr, tb, q, live, sqr, U.p, store);
     if (bad != 0) {  // (wave-uniform) the unproven blocks, listed by their lane 4b
       const bool mine = ((bad >> lane) & 1u) && q == 0 && live;
       const uint64_t m = __ballot(mine);
@@ -247,13 +262,13 @@ __global__ __launch_bounds__(64 * kFixWaves) void k_fdct_fix(const uint8_t* __re
     uint32_t xr[4];
     fdct_load(img, q, xr);
 #if MYYUV_K1_BUF
-    fdct_exact(xr, tb, q, sqr, U.p, [&](const uint32_t (&cc)[16]) { store_block_rows_buf(cc, q, real, g, rs, szz + 2 * q); });
+    fdct_exact(xr, tb, q, sqr, U.p, [&](const uint32_t (&cc)[16]) { store_block_rows_buf(cc, q, real, g, rs, szz); });
 #else
-    uint4* dlo = real ? coef + coef_quad(g, 2 * q) : sink + lane;
-    uint4* dhi = real ? coef + coef_quad(g, 2 * q + 1) : sink + 64 + lane;
+    uint4* dlo = real ? coef + coef_quad(g, q) : sink + lane;
+    uint4* dhi = real ? coef + coef_quad(g, q + 4) : sink + 64 + lane;
     fdct_exact(xr, tb, q, sqr, U.p,
                [&](const uint32_t (&cc)[16]) {
-                 store_block_rows(cc, q, lane, real, g, dlo, dhi, rmask, binfo, szz + 2 * q, sink);
+                 store_block_rows(cc, q, lane, real, g, dlo, dhi, rmask, binfo, szz, sink);
                });
 #endif
   }
@@ -577,9 +592,10 @@ __global__ __launch_bounds__(64) void k_bmp_fdct(const uint8_t* __restrict__ src
     const bool lv = b < U.nlive;
     const uint32_t g = blockIdx.y * G.cum[3] + (U.p == 0 ? G.cum[0] : (U.p == 1 ? G.cum[1] : G.cum[2])) +
                        bf::plane_block(M, S, U, lv ? b : 0u);
-    fdct_core(img + bf::kSlotBytes * (U.slot0 + b), tb, q, sqr, U.p, [&](const uint32_t (&c)[16], bool keep) {
-      store_block_rows_buf(c, q, lv && keep, g, rs, szz + 2 * q);
-    });
+    fdct_core(img + bf::kSlotBytes * (U.slot0 + b), tb, q, lv, sqr, U.p,
+              [&](const uint32_t (&c)[16], bool keep, auto hz) {
+                store_block_rows_buf<decltype(hz)::value>(c, q, lv && keep, g, rs, szz);
+              });
     wave_sync();  // the next unit rewrites the tile
   }
 }

@@ -108,7 +108,8 @@ __device__ __forceinline__ uint32_t first_unit() {
 __device__ __forceinline__ uint32_t unit_stride() { return gridDim.x * 4u; }
 
 // Stage 2 of either transform for one lane's row pair: out[2v + h] =
-// sum_k P[2k + h] * B(v, k) (h = row 2q + h), k ascending, with
+// sum_k P[2k + h] * B(v, k) (h = row 2q + h; K1's exact path: row q + 4h), k
+// ascending, with
 // B(v, k) = D[v][k] (forward: T * D^T) or D[k][v] (inverse: U * D).
 // kSkip: a step k whose P[2k], P[2k+1] are zero in every lane of the wave is
 // skipped (the sums start at +0 and a +-0 product leaves a sum unchanged, so
@@ -157,6 +158,32 @@ __device__ __forceinline__ void transpose_tile(float* tb, uint32_t q, const floa
 #pragma unroll
   for (int k = 0; k < 8; k++) {
     const float2 v = *reinterpret_cast<const float2*>(tb + tix(2 * q, k));
+    P[2 * k] = v.x;
+    P[2 * k + 1] = v.y;
+  }
+}
+
+// The forward transform's tile: rows i = m, m + 4 interleaved, so a stage-2
+// lane reads its pair (M[q][k], M[q + 4][k]) in one 8-byte read.  Rows 4..7
+// are then the second row of every lane, which is what lets a wave leave them
+// out together (fdct_fast).  The banks are tix()'s: the read is word
+// 72 b + 18 q + 2 k as there (conflict-free), and the write of row i, column
+// 2q (+1) is word 72 b + 4 q + const (const = 18 (i & 3) + (i >> 2) (+2)
+// instead of 18 (i >> 1) + (i & 1)), the same 2-way pattern over the lanes.
+__device__ __forceinline__ constexpr int tixf(int i, int j) { return (i & 3) * 18 + 2 * j + (i >> 2); }
+
+// Column pairs (2q, 2q+1) of a block's 8x8 tile after the forward stage 1,
+// read back as the row pair (q, q + 4): P[2k + h] = M[q + 4h][k].
+__device__ __forceinline__ void transpose_fwd(float* tb, uint32_t q, const float (&M)[16], float (&P)[16]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    tb[tixf(i, 2 * q)] = M[2 * i];
+    tb[tixf(i, 2 * q + 1)] = M[2 * i + 1];
+  }
+  wave_sync();
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const float2 v = *reinterpret_cast<const float2*>(tb + tixf(q, k));
     P[2 * k] = v.x;
     P[2 * k + 1] = v.y;
   }
@@ -235,9 +262,10 @@ __device__ __forceinline__ void fdct_stage1_exact(const uint32_t (&xr)[4], float
 // 16-block unit (K1's per-unit body, DCT.cpp:269-277, :297-306), in three
 // pieces: fdct_load (the lane's pixel columns from the block's 8 x 8 B image
 // img, which aliases its transpose tile tb), fdct_fast and fdct_exact.  The
-// lane's 16 coefficients go to emit(c): c[2v + h] holds, in its low 16 bits,
-// the int16 coefficient of row 2q + h, column v.  sqr: the Q tables, their
-// reciprocals and the fast path's row bounds (QTables layout), p the plane.
+// lane's 16 coefficients go to emit(c, ...): c[2v + h] holds, in its low 16
+// bits, the int16 coefficient of row q + 4h, column v (stage 2 owns rows q
+// and q + 4: transpose_fwd).  sqr: the Q tables, their reciprocals and the
+// fast path's row bounds (QTables layout), p the plane.
 //
 // Fast path (round 5): both stages as even/odd butterflies over a nominal
 // basis (fdct_bfly.h: 4.5 instructions per output and stage against round
@@ -252,6 +280,19 @@ __device__ __forceinline__ void fdct_stage1_exact(const uint32_t (&xr)[4], float
 // 17,766 units take the exact path (0.08 %; 20 % at q=90, 52 % at q=100;
 // tools/diag/fdct_bfly_check.cpp, which also checks every passing unit
 // against the reference transform).
+//
+// Zero rows: at q50 rows 4..7 of almost every block quantise to nothing.
+// After the transpose each lane tests its row q + 4 with bfly_zero_row
+// (fdct_bfly.h: 7 adds, an fma, a multiply), and when every storing lane of
+// the wave passes, the wave leaves the h = 1 half of stage 2 out: those
+// coefficients are proven zero and proven the reference's, and emit gets
+// HiZero<true> (76 % of the bench frame's units, tools/diag/
+// k1_zero_rows_sim.py).  Lanes that store nothing (`live` false) do not vote.
+// Planes whose table makes passing rare are not tested (bfly_zero_rows_tested).
+template <bool kZero>
+struct HiZero {
+  static constexpr bool value = kZero;  // rows 4..7 of the unit's blocks are zero: c[2v + 1] == 0
+};
 
 // The lane's columns 2q, 2q+1 of the block's 8 rows, as unsigned pixels:
 // xr[m] = rows 2m (low half), 2m+1 (high half).  The image may be overwritten
@@ -269,11 +310,12 @@ constexpr int kSqR = 3 * 64, kSqKb = 2 * 3 * 64, kSqWords = 2 * 3 * 64 + 3 * 8;
 
 // Returns 0 when every output of the unit is proven (all emitted), else the
 // ballot of the lanes whose BLOCK has an unproven output: with kPerBlock the
-// proven blocks are emitted (emit(c, keep): keep false for the others, whose
-// lanes must store nothing), without it nothing is emitted.
+// proven blocks are emitted (emit(c, keep, hz): keep false for the others,
+// whose lanes must store nothing), without it nothing is emitted.  hz is
+// HiZero<true> when the wave skipped rows 4..7, else HiZero<false>.
 template <bool kPerBlock, class Emit>
-__device__ __forceinline__ uint64_t fdct_fast(const uint32_t (&xr)[4], float* tb, uint32_t q, const float* sqr, int p,
-                                              Emit&& emit) {
+__device__ __forceinline__ uint64_t fdct_fast(const uint32_t (&xr)[4], float* tb, uint32_t q, bool live,
+                                              const float* sqr, int p, Emit&& emit) {
   // ---- A = sum |x - 128| over the block (exact: byte SADs against 128, the
   // block's four lanes summed)
   uint32_t a = 0;
@@ -293,17 +335,18 @@ __device__ __forceinline__ uint64_t fdct_fast(const uint32_t (&xr)[4], float* tb
 #pragma unroll
     for (int i = 0; i < 8; i++) T[2 * i + c] = t[i];
   }
-  float P[16];  // P[2k + h] = T[2q + h][k]
-  transpose_tile(tb, q, T, P);
+  float P[16];  // P[2k + h] = T[q + 4h][k]
+  transpose_fwd(tb, q, T, P);
   // ---- stage 2: the lane's two rows, each quantised as it is done:
   // coef = (int16)roundf(Y / Q) (DCT.cpp:273-276) as rint(Y * fl(1/Q)) where
   // no output lies within beta_h of a half-integer
   const float af = (float)a;
-  const float* Rq = sqr + kSqR + p * 64 + 16u * q;  // reciprocals of rows 2q, 2q+1
+  const float* Rq = sqr + kSqR + p * 64 + 8u * q;  // reciprocals of row q; row q + 4 is 32 further
+  const float* kb = sqr + kSqKb + p * 8 + q;       // kb[4h]: the bound of row q + 4h
   uint32_t c[16];
-  float mx = 0.0f;  // max over the lane's rows of max |e| + beta_h: >= 0.5 when an output may round otherwise
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
+  // one row: returns max |e| + beta_h, >= 0.5 when an output may round otherwise
+  auto row = [&](auto hc) {
+    constexpr int h = decltype(hc)::value ? 1 : 0;
     float x[8], y[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) x[k] = P[2 * k + h];
@@ -311,29 +354,53 @@ __device__ __forceinline__ uint64_t fdct_fast(const uint32_t (&xr)[4], float* tb
     float em = 0.0f;
 #pragma unroll
     for (int v = 0; v < 8; v++) {
-      const float t = y[v] * Rq[8 * h + v];
+      const float t = y[v] * Rq[32 * h + v];
       const float u = t + kMagic;
       const float e = t - (u - kMagic);
       em = __builtin_fmaxf(em, __builtin_fabsf(e));
       c[2 * v + h] = bits(u);
     }
-    mx = __builtin_fmaxf(mx, __builtin_fmaf(af, sqr[kSqKb + p * 8 + 2 * q + h], em));
+    return __builtin_fmaf(af, kb[4 * h], em);
+  };
+  // the tail: mx the maximum over the lane's rows
+  auto finish = [&](float mx, auto hz) -> uint64_t {
+    const uint64_t bad = __builtin_amdgcn_ballot_w64(mx >= 0.5f);
+    if (bad == 0) {
+      emit(c, true, hz);  // every output clears the bound: its rounded t is the reference's coefficient
+      return 0;
+    }
+    if (!kPerBlock) return bad;
+    // (bad != 0 is wave-uniform: the whole wave runs the quad exchanges) a
+    // block is unproven when any of its four lanes is; the bound is per block
+    // (A and the row factors are the block's own), so the other blocks' outputs
+    // are the reference's
+    uint32_t fb = mx >= 0.5f ? 1u : 0u;
+    fb |= quad_xor1(fb);
+    fb |= quad_xor2(fb);
+    emit(c, fb == 0u, hz);
+    return __builtin_amdgcn_ballot_w64(fb != 0u);
+  };
+  // ---- rows 4..7 proven zero in every storing block of the wave: their
+  // half of stage 2 is left out (the rule implies the row's proof, so the
+  // blocks' verdicts below are what they would have been)
+  bool skip = false;
+  // (wave-uniform, through an SGPR: the plane's kb[4]) planes with small
+  // quantisers are not tested, fdct_bfly.h
+  const float kb4 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(bits(sqr[kSqKb + p * 8 + 4])));
+  if (myyuv_bfly::bfly_zero_rows_tested(kb4)) {
+    float x1[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) x1[k] = P[2 * k + 1];
+    const bool zr = myyuv_bfly::bfly_zero_row(x1, af, kb[4]) || !live;
+    skip = __builtin_amdgcn_ballot_w64(zr) == ~0ull;
   }
-  const uint64_t bad = __builtin_amdgcn_ballot_w64(mx >= 0.5f);
-  if (bad == 0) {
-    emit(c, true);  // every output clears the bound: its rounded t is the reference's coefficient
-    return 0;
+  const float m0 = row(HiZero<false>{});
+  if (skip) {  // (wave-uniform)
+#pragma unroll
+    for (int v = 0; v < 8; v++) c[2 * v + 1] = 0u;
+    return finish(m0, HiZero<true>{});
   }
-  if (!kPerBlock) return bad;
-  // (bad != 0 is wave-uniform: the whole wave runs the quad exchanges) a
-  // block is unproven when any of its four lanes is; the bound is per block
-  // (A and the row factors are the block's own), so the other blocks' outputs
-  // are the reference's
-  uint32_t fb = mx >= 0.5f ? 1u : 0u;
-  fb |= quad_xor1(fb);
-  fb |= quad_xor2(fb);
-  emit(c, fb == 0u);
-  return __builtin_amdgcn_ballot_w64(fb != 0u);
+  return finish(__builtin_fmaxf(m0, row(HiZero<true>{})), HiZero<false>{});
 }
 
 // The unit in the reference's order (the tile tb is rewritten: callers
@@ -341,16 +408,16 @@ __device__ __forceinline__ uint64_t fdct_fast(const uint32_t (&xr)[4], float* tb
 template <class Emit>
 __device__ __forceinline__ void fdct_exact(const uint32_t (&xr)[4], float* tb, uint32_t q, const float* sqr, int p,
                                            Emit&& emit) {
-  const uint32_t n0 = 16u * q;
+  const uint32_t n0 = 8u * q;
   float T[16];
   fdct_stage1_exact(xr, T);
-  float P[16];  // P[2k + h] = T[2q + h][k]
-  transpose_tile(tb, q, T, P);
-  float Y[16];  // Y[2v + h] = Y[2q + h][v]
+  float P[16];  // P[2k + h] = T[q + 4h][k]
+  transpose_fwd(tb, q, T, P);
+  float Y[16];  // Y[2v + h] = Y[q + 4h][v]
   dot_rows<false>(P, Y);
-  // reciprocals of rows 2q, 2q+1 (natural n0 .. n0 + 15)
+  // reciprocals of rows q (natural n0 .. n0 + 7) and q + 4 (32 further)
   const float4* R4 = reinterpret_cast<const float4*>(sqr + kSqR + p * 64 + n0);
-  const float4 r0 = R4[0], r1 = R4[1], r2 = R4[2], r3 = R4[3];
+  const float4 r0 = R4[0], r1 = R4[1], r2 = R4[8], r3 = R4[9];
   const float rr[16] = {r0.x, r2.x, r0.y, r2.y, r0.z, r2.z, r0.w, r2.w,
                         r1.x, r3.x, r1.y, r3.y, r1.z, r3.z, r1.w, r3.w};  // [2v + h]
   uint32_t c[16];
@@ -366,38 +433,44 @@ __device__ __forceinline__ void fdct_exact(const uint32_t (&xr)[4], float* tb, u
   if (mx >= 0.5f) {  // a near-tie in the lane: the reference's divide for all 16
     const float* Qt = sqr + p * 64 + n0;
 #pragma unroll
-    for (int j = 0; j < 16; j++) c[j] = (uint32_t)(int)roundf(Y[j] / Qt[(j >> 1) + 8 * (j & 1)]);
+    for (int j = 0; j < 16; j++) c[j] = (uint32_t)(int)roundf(Y[j] / Qt[(j >> 1) + 32 * (j & 1)]);
   }
   emit(c);
 }
 
 // Both in one pass (the fused encoder): the fast path, else the exact one.
+// live: the lane's block is stored (the others do not vote on the zero rows).
 template <class Emit>
-__device__ __forceinline__ void fdct_core(const uint8_t* img, float* tb, uint32_t q, const float* sqr, int p,
-                                          Emit&& emit) {
+__device__ __forceinline__ void fdct_core(const uint8_t* img, float* tb, uint32_t q, bool live, const float* sqr,
+                                          int p, Emit&& emit) {
   uint32_t xr[4];
   fdct_load(img, q, xr);
-  if (__builtin_expect(fdct_fast<false>(xr, tb, q, sqr, p, emit) != 0, 0)) {
+  if (__builtin_expect(fdct_fast<false>(xr, tb, q, live, sqr, p, emit) != 0, 0)) {
     wave_sync();
-    fdct_exact(xr, tb, q, sqr, p, [&](const uint32_t (&c)[16]) { emit(c, true); });
+    fdct_exact(xr, tb, q, sqr, p, [&](const uint32_t (&c)[16]) { emit(c, true, HiZero<false>{}); });
   }
 }
 
-// Rows 2q, 2q+1 of the block as two coefficient quads (codec_common.hpp
-// layout) and the block's row mask (bit c: row c has a nonzero coefficient),
-// from its four lanes (lanes 4b .. 4b+3 of the wave).
+// Rows q (lo) and q + 4 (hi) of the block as two coefficient quads
+// (codec_common.hpp layout) and the block's row mask (bit c: row c has a
+// nonzero coefficient), from its four lanes (lanes 4b .. 4b+3 of the wave).
+// kHiZero (wave-uniform, fdct_fast): rows 4..7 are zero, hi is a constant.
+template <bool kHiZero = false>
 __device__ __forceinline__ void pack_quads(const uint32_t (&c)[16], uint32_t q, uint4& lo, uint4& hi,
                                            uint32_t& rm) {
   lo.x = __builtin_amdgcn_perm(c[2], c[0], 0x05040100u);
   lo.y = __builtin_amdgcn_perm(c[6], c[4], 0x05040100u);
   lo.z = __builtin_amdgcn_perm(c[10], c[8], 0x05040100u);
   lo.w = __builtin_amdgcn_perm(c[14], c[12], 0x05040100u);
-  hi.x = __builtin_amdgcn_perm(c[3], c[1], 0x05040100u);
-  hi.y = __builtin_amdgcn_perm(c[7], c[5], 0x05040100u);
-  hi.z = __builtin_amdgcn_perm(c[11], c[9], 0x05040100u);
-  hi.w = __builtin_amdgcn_perm(c[15], c[13], 0x05040100u);
-  const bool nzl = (lo.x | lo.y | lo.z | lo.w) != 0u, nzh = (hi.x | hi.y | hi.z | hi.w) != 0u;
-  rm = (nzl ? 1u << (2 * q) : 0u) | (nzh ? 2u << (2 * q) : 0u);
+  hi = make_uint4(0, 0, 0, 0);
+  if (!kHiZero) {
+    hi.x = __builtin_amdgcn_perm(c[3], c[1], 0x05040100u);
+    hi.y = __builtin_amdgcn_perm(c[7], c[5], 0x05040100u);
+    hi.z = __builtin_amdgcn_perm(c[11], c[9], 0x05040100u);
+    hi.w = __builtin_amdgcn_perm(c[15], c[13], 0x05040100u);
+  }
+  const bool nzl = (lo.x | lo.y | lo.z | lo.w) != 0u, nzh = !kHiZero && (hi.x | hi.y | hi.z | hi.w) != 0u;
+  rm = (nzl ? 1u << q : 0u) | (nzh ? 16u << q : 0u);
   rm |= quad_xor1(rm);
   rm |= quad_xor2(rm);
 }
