@@ -29,6 +29,12 @@
 // (requantise, include/myyuv_hip.h: no pixels in between; the qualities parse
 // and fill as -compress DCT's):
 //   myyuv_cli in.myyuv -requantize q [q [q]] -o out.myyuv
+// a compressed input as a baseline JPEG file written from its coefficients
+// (export to JPEG, include/myyuv_hip.h); with -q an uncompressed input,
+// compressed at those qualities and exported without the stream leaving the
+// device:
+//   myyuv_cli in.myyuv -to_jpeg -o out.jpg
+//   myyuv_cli raw.myyuv -to_jpeg -q q [q [q]] -o out.jpg
 // a compressed input mirrored, rotated or transposed on its coefficients
 // (transform, include/myyuv_hip.h; -q: re-encoded at those qualities on the
 // way, otherwise at its own):
@@ -100,6 +106,9 @@ void usage() {
             << "      (-scale: a compressed image at that size, straight from its DCT coefficients)\n"
             << "  myyuv_cli IMAGE.myyuv -requantize Q [Q [Q]] -o OUT.myyuv\n"
             << "      (a compressed image at another quality, straight from its DCT coefficients)\n"
+            << "  myyuv_cli IMAGE.myyuv -to_jpeg [-q Q [Q [Q]]] -o OUT.jpg\n"
+            << "      (a baseline JPEG straight from a compressed image's DCT coefficients; -q: an uncompressed\n"
+            << "       image, compressed at those qualities and exported on the GPU)\n"
             << "  myyuv_cli IMAGE.myyuv -transform flip_h|flip_v|rot180|transpose|transverse|rot90|rot270"
                " [-q Q [Q [Q]]] -o OUT.myyuv\n"
             << "      (a compressed image mirrored, rotated or transposed, straight from its DCT coefficients)\n"
@@ -401,6 +410,44 @@ int run_yuv(const myyuv::YUV& yuv, size_t a, const std::vector<std::string>& arg
     });
     std::cout << "YUV DCT requantization (" << label << ") : " << ms << " ms\n";
     out.dump(args[a]);
+    return 0;
+  }
+  if (cmd == "-to_jpeg") {  // [-q Q [Q [Q]]] -o OUT.jpg: -q for a raw input (and only then), as -compress DCT's
+    a++;
+    const bool with_q = a < args.size() && args[a] == "-q";
+    std::vector<std::string> params;
+    if (with_q) a++;
+    while (a < args.size() && args[a] != "-o") params.push_back(args[a++]);
+    a++;
+    if (a >= args.size() || args.size() != a + 1 || (!with_q && !params.empty())) {
+      std::cout << "Invalid argument, last arguments must be `-o /path/to/new_image.jpg`\n";
+      usage();
+      return 1;
+    }
+    if (yuv.isCompressed() && with_q) {
+      std::cout << "Invalid argument, -to_jpeg takes -q for an uncompressed image only (a compressed one is "
+                   "exported at its own qualities; -requantize changes them)\n";
+      return 1;
+    }
+    if (!yuv.isCompressed() && !with_q) {
+      std::cout << "Invalid argument, -to_jpeg of an uncompressed image needs `-q Q [Q [Q]]`\n";
+      usage();
+      return 1;
+    }
+    std::vector<uint8_t> file;
+    const float ms = elapsed_ms([&] {
+      if (with_q) {
+        uint8_t q[3];
+        dct_qualities(params, q);
+        file = yuv.to_jpeg({q[0], q[1], q[2]});  // compressed and exported on the device
+      } else {
+        file = yuv.to_jpeg();
+      }
+    });
+    std::cout << "YUV DCT to JPEG : " << ms << " ms\n";
+    std::ofstream f(args[a], std::ios::binary);
+    f.write(reinterpret_cast<const char*>(file.data()), (std::streamsize)file.size());
+    if (!f) throw std::runtime_error("Error writing " + args[a]);
     return 0;
   }
   if (cmd == "-transform") {  // OP [-q Q [Q [Q]]] -o OUT.myyuv: the qualities as -compress DCT's

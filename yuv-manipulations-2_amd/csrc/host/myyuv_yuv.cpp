@@ -529,6 +529,52 @@ YUV YUV::compress_to_psnr(double db, myyuv_target_result* result) const {
   return compressed_like(*this, r.quality, payload.data(), size);
 }
 
+namespace {
+
+// One call with room for `first` bytes, and once more at the size the call
+// reports when the file is larger: no buffer of myyuv_jpeg_bound's size.
+template <class Call>
+std::vector<uint8_t> jpeg_file(uint32_t first, Call call) {
+  std::vector<uint8_t> out(first);
+  uint32_t size = 0;
+  int rc = call(out.data(), (uint32_t)out.size(), &size);
+  if (rc == MYYUV_E_CAPACITY) {
+    out.resize(size);
+    rc = call(out.data(), (uint32_t)out.size(), &size);
+  }
+  if (rc) fail(rc);
+  out.resize(size);
+  return out;
+}
+
+}  // namespace
+
+std::vector<uint8_t> YUV::to_jpeg() const {
+  if (getFormatGroup() != FormatGroup::PLANAR) throw std::runtime_error("Error decompressing: YUV must be planar");
+  if (getCompression() != Compressions::DCT)
+    throw std::runtime_error("Error exporting: image is not compressed (to_jpeg needs DCT coefficients)");
+  if (header.compression_params_size != 3 || !compression_params)
+    throw std::runtime_error("Error decompression: incorrect parameters count. 3 parameters required");
+  for (int p = 0; p < 3; p++)
+    if (compression_params[p] < 1 || compression_params[p] > 100)
+      throw std::runtime_error("Level of quality must be between 1 and 100");
+  return jpeg_file(header.data_size + 1024, [this](uint8_t* out, uint32_t cap, uint32_t* size) {
+    int64_t bad = -1;
+    return myyuv_gpu_dct_to_jpeg(t_codec.get(), data, header.data_size, header.width, header.height,
+                                 compression_params, out, cap, size, &bad);
+  });
+}
+
+std::vector<uint8_t> YUV::to_jpeg(const std::array<uint8_t, 3>& q) const {
+  raw_planar_ok(*this);
+  for (uint8_t v : q)
+    if (v < 1 || v > 100) throw std::runtime_error("Level of quality must be between 1 and 100");
+  const uint32_t first = std::max<uint32_t>(4096, header.width / 4 * header.height);
+  return jpeg_file(first, [this, &q](uint8_t* out, uint32_t cap, uint32_t* size) {
+    return myyuv_gpu_iyuv_to_jpeg(t_codec.get(), data, header.width, header.height, q.data(), out, cap, size);
+  });
+}
+
 }  // namespace myyuv
 
 namespace myyuvDCT {

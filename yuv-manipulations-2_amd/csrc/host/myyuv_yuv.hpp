@@ -114,6 +114,14 @@ class YUV {
   myyuv_probe probe(const std::array<uint8_t, 3>& q) const;
   YUV compress_to_size(uint32_t payload_bytes, myyuv_target_result* result = nullptr) const;
   YUV compress_to_psnr(double db, myyuv_target_result* result = nullptr) const;
+  // Export to JPEG (include/myyuv_hip.h): the baseline JPEG file of a
+  // DCT-compressed planar frame, written from its coefficients.  An
+  // uncompressed frame: std::runtime_error("Error exporting: image is not
+  // compressed (to_jpeg needs DCT coefficients)"); a malformed stream: the
+  // decompressor's messages.  With qualities, on an UNCOMPRESSED planar frame:
+  // the file of compress at q, the stream never leaving the device.
+  std::vector<uint8_t> to_jpeg() const;
+  std::vector<uint8_t> to_jpeg(const std::array<uint8_t, 3>& q) const;
   void load(const std::string& path);
   void load(const BMP& bmp, FourccFormat format);
   void dump(const std::string& path) const;

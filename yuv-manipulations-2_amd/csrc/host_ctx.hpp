@@ -17,6 +17,7 @@
 #include "bmp_fdct.h"
 #include "codec_common.hpp"
 #include "downscale.h"
+#include "jpeg_export.h"
 #include "k_chain.hpp"
 #include "k_stream.hpp"
 #include "myyuv_hip.h"
@@ -52,6 +53,12 @@ __global__ void k_requant(const uint8_t*, const uint32_t*, uint32_t, const Strea
 __global__ void k_coef_xform(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
                              const uint32_t*, FrameGeom, uint32_t, uint32_t, const RequantTables*, uint32_t, uint32_t,
                              uint4*, uint4*, uint8_t*, uint32_t*, unsigned long long*);
+template <bool Write>
+__global__ void k_jpeg_export(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*, const uint32_t*,
+                              const uint32_t*, FrameGeom, uint32_t, uint32_t, uint4*, uint32_t*, const uint32_t*,
+                              const uint32_t*, uint8_t*, uint32_t, unsigned long long*);
+__global__ void k_jpeg_place(const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, myyuv_jpeg::Head, uint8_t*,
+                             uint32_t, uint32_t*, unsigned long long*);
 template <uint32_t W>
 __global__ void k_huff_encode(const uint4*, const uint32_t*, const uint4*, FrameGeom, uint32_t*, uint32_t*,
                               uint8_t*, uint32_t*, uint32_t*, uint32_t*);
@@ -256,6 +263,9 @@ struct myyuv_hip_ctx {
   // scan writes, then an error word of its own (the scan reports a head-only
   // capacity as an overflow; nobody reads it); the host-buffer calls' records
   DevBuf pbsz, prec;
+  // export to JPEG: per 64-block group the interval's size (the sizing
+  // launch) and its file offset (k_jpeg_place); the host-buffer calls' file
+  DevBuf jsz, joff, jout;
   // profiling: the kernels' start/stop events until drain_profile reads
   // them; they are used again from launch to launch
   struct Stamp {
@@ -264,8 +274,8 @@ struct myyuv_hip_ctx {
   };
   uint32_t prof = 0;  // bit k: stamp kernel id k
   uint32_t skip = 0;  // diagnostic: bit k: do not launch kernel id k (myyuv_debug_skip_kernels)
-  double ms[MYYUV_K_TOP] = {};
-  int64_t launches[MYYUV_K_TOP] = {};
+  double ms[MYYUV_K_MAX] = {};
+  int64_t launches[MYYUV_K_MAX] = {};
   std::vector<Stamp> pending;
   std::vector<Event> free_events;
   // set once every piece of it exists (pipe_init)

@@ -38,6 +38,7 @@
 #include "downscale.h"
 #include "huff_common.hpp"
 #include "idct_scaled.h"
+#include "jpeg_export.h"
 #include "k1_store.hpp"
 #include "k_metric.hpp"
 #include "k_stream.hpp"
@@ -2078,6 +2079,305 @@ __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_decode_compare(const uin
   uint32_t gl = lane;
   asm volatile("" : "+v"(gl));
   mt::finish(bs, D.live, mt::wave_slot(part), map != nullptr ? map + (D.gbase + D.g0 + gl) : nullptr);
+}
+
+// ---- export to JPEG -------------------------------------------------------
+//
+// k_jpeg_export: a stream's blocks written as the restart intervals of a
+// baseline JPEG (include/myyuv_hip.h, "Export to JPEG"; the code of a block is
+// jpeg_export.h's).  Grid and decode are k_requant's: one wave per 64-block
+// group (blockIdx.x) of frame blockIdx.y, decode_group unchanged, a block with
+// a table that is not "regular" read back from the coefficient buffer.  A
+// group is one plane's consecutive blocks, which is one restart interval of
+// that plane's non-interleaved scan, so the wave owns the interval:
+//   1. lane l's DC prediction is lane l - 1's DC (0 for lane 0);
+//   2. every lane counts its block's bits (jp::BitCount), the wave scans them,
+//      and the last live lane adds the 1-bits that fill the last byte;
+//   3. the lanes write their blocks' bits at their offsets into an LDS bit
+//      image laid over the chunk stage and the value-position table, both dead
+//      after the decode: a 64-bit accumulator per lane, flushed word by word
+//      with ds_or (a word is shared by neighbouring blocks).  Words hold the
+//      stream's bytes most significant first;
+//   4. the wave reads the image 256 bytes at a time, counts each lane's 0xFF
+//      bytes, scans the counts and (Write) stores the bytes with a 0x00 after
+//      every 0xFF at the interval's place in the file.
+// The image holds kJpegImgWords words (7,168 B, about 112 B per block; a
+// natural picture needs 1-2 KB per group).  A longer interval (up to 13,280 B
+// when every coefficient is +-1023) takes several rounds of steps 3 and 4 over
+// consecutive windows of the interval's bits: a lane encodes its block again
+// in every round whose window its bits touch, and the sink drops the words
+// outside the window.
+//
+// Every live lane contributes a block, whatever the stream holds: a lane whose
+// chunk failed, and every lane of a frame whose header k_scan_chain rejected,
+// contributes the all-zero block (k_requant's rule); the error itself is in
+// the shared error word.
+//
+// Write = false: the sizing launch; gbuf[group] = the interval's stuffed bytes.
+// k_jpeg_place then turns the sizes into file offsets (the scan headers, the
+// RST markers and EOI fall between the intervals).  Write = true: the same
+// work again, the bytes stored at out + f * cap_out + goff[group], at most
+// gbuf[group] of them, and nothing for a frame whose file exceeds cap_out.
+// No buffer scales with the worst case: the scratch is two words per group.
+namespace jp = myyuv_jpeg;
+
+__device__ const jp::CodeTables d_jpeg_tab[2] = {jp::kLumTables, jp::kChrTables};
+
+constexpr uint32_t kJpegImgWords = ((kStageQuads + 1 + kGposQuads) * 4) & ~63u;
+constexpr uint32_t kJpegImgBits = kJpegImgWords * 32;
+static_assert(kJpegImgWords * 4 <= sizeof(uint4) * (kStageQuads + 1 + kGposQuads), "the image over the stage");
+static_assert(kJpegImgBits >= 2 * jp::kMaxBlockBits, "a block touches at most two windows");
+
+struct JpegLdsTab {
+  const uint32_t* t;
+  __device__ __forceinline__ uint32_t dc(uint32_t cat) const { return t[256 + cat]; }
+  __device__ __forceinline__ uint32_t ac(uint32_t sym) const { return t[sym]; }
+};
+
+// Bits into the LDS image from bit `pos` of the interval on; w0: the window's
+// first word.  The first word starts with pos & 31 zero bits (a neighbour's).
+struct JpegLdsSink {
+  uint32_t* img;
+  uint32_t w0;
+  uint64_t acc;
+  uint32_t n, wi;
+  __device__ __forceinline__ JpegLdsSink(uint32_t* image, uint32_t first_word, uint32_t pos)
+      : img(image), w0(first_word), acc(0), n(pos & 31u), wi(pos >> 5) {}
+  __device__ __forceinline__ void flush(uint32_t word) {
+    const uint32_t k = wi - w0;  // (below the window: wraps past it)
+    if (k < kJpegImgWords) atomicOr(&img[k], word);
+    wi++;
+  }
+  __device__ __forceinline__ void put(uint32_t bits, uint32_t count) {
+    acc = (acc << count) | bits;
+    n += count;
+    if (n >= 32) {
+      n -= 32;
+      flush((uint32_t)(acc >> n));
+      acc &= (1ull << n) - 1ull;
+    }
+  }
+  __device__ __forceinline__ void finish() {
+    if (n) flush((uint32_t)acc << (32 - n));
+  }
+};
+
+#ifndef MYYUV_JPEG_WAVES
+// waves per SIMD of the register budget (the LDS allows 4.75): the 8192x8192 q50 export took 470 / 389 / 426 /
+// 558 us at 2 / 3 / 4 / 5 (184 VGPRs and no spill at 2; 16 / 69 / 121 spilled registers at 3 / 4 / 5)
+#define MYYUV_JPEG_WAVES 3
+#endif
+template <bool Write>
+__global__ __launch_bounds__(64, MYYUV_JPEG_WAVES) void k_jpeg_export(const uint8_t* __restrict__ in,
+                                                   const uint32_t* __restrict__ in_size,
+                                                   uint32_t cap,
+                                                   const StreamDesc* __restrict__ desc,
+                                                   const uint32_t* __restrict__ local_off,
+                                                   const uint32_t* __restrict__ tile_pre,
+                                                   FrameGeom G, uint32_t tiles_p0,
+                                                   uint32_t tiles_p1, uint4* __restrict__ coef,
+                                                   uint32_t* __restrict__ gbuf,
+                                                   const uint32_t* __restrict__ goff,
+                                                   const uint32_t* __restrict__ out_sizes,
+                                                   uint8_t* __restrict__ out, uint32_t cap_out,
+                                                   unsigned long long* __restrict__ err) {
+  __shared__ uint4 stq[kStageQuads + 1 + kGposQuads];
+  __shared__ uint32_t stab[jp::kTabWords];
+  const uint32_t lane = threadIdx.x;
+  if (lane == 0) stq[kStageQuads] = make_uint4(0u, 0u, 0u, 0u);  // (ordered by decode_group's barrier)
+  {
+    // the plane's code tables (visible after the barrier that follows the decode)
+    const uint32_t t = blockIdx.x;
+    const uint32_t* src = d_jpeg_tab[t >= tiles_p0 ? 1 : 0].e;
+    for (uint32_t k = lane; k < jp::kTabWords; k += kWave) stab[k] = src[k];
+  }
+  DecodeGroup D;
+  uint32_t nw[32];
+#pragma unroll
+  for (int w = 0; w < 32; w++) nw[w] = 0;
+  bool direct;
+  const bool frame_ok = decode_group(in, in_size, cap, desc, local_off, tile_pre, G, tiles_p0, tiles_p1, coef, err,
+                                     stq, D, nw, direct);
+  const bool keep = frame_ok && D.live && D.good;
+  if (keep && direct) {  // decode_general wrote the block to coef (a table the reference never writes)
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      const uint4 v = coef[coef_quad(D.gbase + D.g, c)];
+      nw[4 * c] = v.x;
+      nw[4 * c + 1] = v.y;
+      nw[4 * c + 2] = v.z;
+      nw[4 * c + 3] = v.w;
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < 32; w++) nw[w] = keep ? nw[w] : 0u;
+  __syncthreads();  // the decode's LDS reads are done, the tables are in place
+
+  const uint32_t nlive = D.g1 - D.g0;
+  const bool last = lane + 1 == nlive;
+  const int dc = (int)(int16_t)(nw[0] & 0xFFFFu);
+  const int up = __shfl_up(dc, 1, kWave);
+  const int pred = lane == 0 ? 0 : up;
+  auto cf = [&nw](int k) {
+    const int n = jp::kZigzag[k];
+    const uint32_t w = nw[n >> 1];
+    return (int)(int16_t)((n & 1) ? (w >> 16) : (w & 0xFFFFu));
+  };
+  const JpegLdsTab tab{stab};
+  jp::BitCount cnt;
+  jp::encode_block(cf, pred, tab, cnt);
+  const uint32_t nbits = D.live ? cnt.n : 0u;
+  const uint32_t incl = wave_incl_scan(nbits);
+  const uint32_t pos = incl - nbits;
+  const uint32_t tbits = (uint32_t)__shfl((int)incl, kWave - 1, kWave);
+  const uint32_t pad = (0u - tbits) & 7u;
+  const uint32_t T = tbits + pad;  // a multiple of 8, at least 8
+
+  const uint32_t ntg = gridDim.x;
+  const uint32_t gi = D.f * ntg + blockIdx.x;
+  uint32_t* img = reinterpret_cast<uint32_t*>(stq);
+  uint8_t* q = nullptr;
+  const uint8_t* qend = nullptr;
+  if (Write) {
+    const uint32_t total = out_sizes[D.f];
+    if (total <= cap_out) {
+      const uint32_t o = goff[gi];
+      const uint32_t sz = min(gbuf[gi], total - min(o, total));
+      q = out + (size_t)D.f * cap_out + o;
+      qend = q + sz;
+      // what stands in front of the interval (k_jpeg_place left room for it,
+      // after the file header: o >= kHeaderBytes + kSosBytes): the plane's
+      // scan header, or RSTm with m counted within the plane
+      const uint32_t t = blockIdx.x;
+      const uint32_t tp = t - (D.p == 0 ? 0u : (D.p == 1 ? tiles_p0 : tiles_p0 + tiles_p1));
+      if (lane == 0 && o >= jp::kHeaderBytes + jp::kSosBytes && o <= total) {
+        if (tp == 0) {
+          jp::write_sos(q - jp::kSosBytes, (uint32_t)D.p);
+        } else {
+          q[-2] = 0xFF;
+          q[-1] = (uint8_t)(0xD0u + ((tp - 1u) & 7u));
+        }
+      }
+    }
+  }
+  uint32_t nff = 0;  // the 0xFF bytes of the windows so far
+  for (uint32_t b0 = 0; b0 < T; b0 += kJpegImgBits) {
+    const uint32_t wbits = min(T - b0, kJpegImgBits);
+    for (uint32_t k = lane; k < (wbits + 31) >> 5; k += kWave) img[k] = 0u;
+    __syncthreads();
+    const uint32_t end = pos + nbits + (last ? pad : 0u);
+    if (D.live && end > b0 && pos < b0 + wbits) {
+      JpegLdsSink sink(img, b0 >> 5, pos);
+      jp::encode_block(cf, pred, tab, sink);
+      if (last && pad) sink.put((1u << pad) - 1u, pad);
+      sink.finish();
+    }
+    __syncthreads();
+    const uint32_t wbytes = wbits >> 3;
+    for (uint32_t j0 = 0; j0 < wbytes; j0 += 4 * kWave) {
+      const uint32_t j = j0 + 4 * lane;
+      const uint32_t nb = j < wbytes ? min(4u, wbytes - j) : 0u;
+      const uint32_t word = nb ? img[j >> 2] : 0u;
+      uint32_t ff = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < 4; k++) ff += (k < nb && ((word >> (24 - 8 * k)) & 0xFFu) == 0xFFu) ? 1u : 0u;
+      const uint32_t fincl = wave_incl_scan(ff);
+      if (Write && q != nullptr) {
+        uint8_t* o = q + ((b0 >> 3) + j + nff + fincl - ff);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+          const uint32_t b = (word >> (24 - 8 * k)) & 0xFFu;
+          if (k < nb) {
+            if (o < qend) *o = (uint8_t)b;
+            o++;
+            if (b == 0xFFu) {
+              if (o < qend) *o = 0;
+              o++;
+            }
+          }
+        }
+      }
+      nff += (uint32_t)__shfl((int)fincl, kWave - 1, kWave);
+    }
+    __syncthreads();  // the image is zeroed again
+  }
+  if (!Write && lane == 0) gbuf[gi] = (T >> 3) + nff;
+}
+template __global__ void k_jpeg_export<false>(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
+                                              const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t, uint4*,
+                                              uint32_t*, const uint32_t*, const uint32_t*, uint8_t*, uint32_t,
+                                              unsigned long long*);
+template __global__ void k_jpeg_export<true>(const uint8_t*, const uint32_t*, uint32_t, const StreamDesc*,
+                                             const uint32_t*, const uint32_t*, FrameGeom, uint32_t, uint32_t, uint4*,
+                                             uint32_t*, const uint32_t*, const uint32_t*, uint8_t*, uint32_t,
+                                             unsigned long long*);
+
+// k_jpeg_place: one workgroup per frame turns the groups' interval sizes into
+// file offsets and writes the file header and EOI.  In front of group t's
+// interval stands its plane's scan header (the plane's first group) or the
+// marker RSTm, m = (t - 1) mod 8 counted within the plane: the placement
+// leaves room for them, the writing launch's waves write them with their
+// intervals.  goff[t]: the file offset of the interval's first
+// byte; out_sizes[f]: the file's size (0xFFFFFFFF when it does not fit 32
+// bits).  A file beyond cap_out is MYYUV_E_CAPACITY (no block) and nothing of
+// it is written; out == nullptr: sizes and offsets only.
+__global__ __launch_bounds__(256) void k_jpeg_place(const uint32_t* __restrict__ gsize, uint32_t* __restrict__ goff,
+                                                    uint32_t t0, uint32_t t1, uint32_t t2, jp::Head H,
+                                                    uint8_t* __restrict__ out, uint32_t cap_out,
+                                                    uint32_t* __restrict__ out_sizes,
+                                                    unsigned long long* __restrict__ err) {
+  // kPer consecutive groups per thread and round: a thread's own sum (below
+  // 2^32: at most 16 x 26.6 KB), the wave's scan by DPP, the four waves'
+  // totals through LDS; the running offset in 64 bits
+  constexpr uint32_t kPer = 16;
+  __shared__ uint32_t wsum[4];
+  const uint32_t f = blockIdx.x, tid = threadIdx.x, ntg = t0 + t1 + t2;
+  gsize += (size_t)f * ntg;
+  goff += (size_t)f * ntg;
+  unsigned long long run = jp::kHeaderBytes;
+  for (uint32_t base = 0; base < ntg; base += 256 * kPer) {
+    const uint32_t tb = base + tid * kPer;
+    uint32_t v[kPer], own = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; i++) {
+      const uint32_t t = tb + i;
+      const bool first = t == 0 || t == t0 || t == t0 + t1;
+      v[i] = t < ntg ? gsize[t] : 0u;
+      own += t < ntg ? v[i] + (first ? jp::kSosBytes : 2u) : 0u;
+    }
+    const uint32_t incl = wave_incl_scan(own);
+    if ((tid & 63u) == 63u) wsum[tid >> 6] = incl;
+    __syncthreads();
+    unsigned long long at = run + (incl - own);  // the end of the interval before this thread's first
+    unsigned long long all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+      at += k < (tid >> 6) ? wsum[k] : 0u;
+      all += wsum[k];
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kPer; i++) {
+      const uint32_t t = tb + i;
+      const bool first = t == 0 || t == t0 || t == t0 + t1;
+      at += first ? jp::kSosBytes : 2u;  // the scan header or the marker in front of the interval
+      if (t < ntg) goff[t] = (uint32_t)min(at, 0xFFFFFFFFull);
+      at += v[i];
+    }
+    run += all;
+    __syncthreads();  // (wsum is written again)
+  }
+  const unsigned long long total = run + 2;
+  if (tid == 0) {
+    out_sizes[f] = (uint32_t)min(total, 0xFFFFFFFFull);
+    if (total > cap_out) record_error(err, 0, 5 /* MYYUV_E_CAPACITY, any frame */);
+  }
+  if (out == nullptr || total > cap_out) return;
+  out += (size_t)f * cap_out;
+  for (uint32_t k = tid; k < jp::kHeaderBytes; k += 256) out[k] = H.b[k];
+  if (tid == 0) {
+    out[total - 2] = 0xFF;
+    out[total - 1] = 0xD9;
+  }
 }
 
 }  // namespace myyuv_gpu

@@ -840,8 +840,11 @@ const char* myyuv_hip_strerror(int code) {
 
 const char* myyuv_hip_error_message(int code) {
   if (code == MYYUV_E_TARGET) return "target not reachable";
+  if (code == MYYUV_E_JPEG_DIM) return "JPEG width and height must not exceed 65535";
   return myyuv_hip_strerror(code);
 }
+
+uint64_t myyuv_jpeg_bound(uint32_t w, uint32_t h) { return myyuv_jpeg::file_bound(w, h); }
 
 uint32_t myyuv_dct_payload_bound(uint32_t w, uint32_t h) {
   const uint64_t nb = (uint64_t)(w / 8) * (h / 8) + 2ull * (uint64_t)(w / 16) * (h / 16);
@@ -2092,6 +2095,193 @@ int myyuv_gpu_dct_transform_device(myyuv_hip_handle c, const void* d_payload, co
                        d_out_sizes, stream);
 }
 
+// ---- export to JPEG (defined in myyuv_hip.h) --------------------------------
+namespace {
+
+// Two launches of one kernel with a scan between them ("Export
+// to JPEG"): the sizing launch leaves every group's interval size, k_jpeg_place
+// turns the sizes into file offsets and writes the header and the markers, the
+// writing launch stores the intervals.  Workspace: the decoder's coefficient
+// image and scan, and two words per 64-block group.
+int reserve_jpeg(myyuv_hip_ctx* c, const FrameGeom& G, uint32_t ntg) {
+  const uint32_t nwaves = ceil_div(G.cum[3] * G.nframes, kWave);
+  int e = c->coef.grow((size_t)nwaves * kCoefQuadsPerWave * 16);
+  e |= reserve_scan(c, G);
+  e |= c->psize.grow(8);
+  e |= c->jsz.grow((size_t)ntg * G.nframes * 4);
+  e |= c->joff.grow((size_t)ntg * G.nframes * 4);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+struct JpegTiles {
+  uint32_t t0, t1, t2;
+  explicit JpegTiles(const FrameGeom& G)
+      : t0(ceil_div(G.cum[1] - G.cum[0], kWave)),
+        t1(ceil_div(G.cum[2] - G.cum[1], kWave)),
+        t2(ceil_div(G.cum[3] - G.cum[2], kWave)) {}
+  uint32_t n() const { return t0 + t1 + t2; }
+};
+
+int launch_jpeg_export(bool write, myyuv_hip_ctx* c, const FrameGeom& G, const uint8_t* in,
+                       const uint32_t* d_size_in, uint32_t cap_in, const uint32_t* d_size_out, uint8_t* d_out,
+                       uint32_t cap_out, hipStream_t s) {
+  const JpegTiles T(G);
+  return launch(c, MYYUV_K_JPEG, write ? k_jpeg_export<true> : k_jpeg_export<false>, dim3(T.n(), G.nframes), dim3(kWave), s, in, d_size_in,
+                cap_in, (const StreamDesc*)c->desc.as<StreamDesc>(), c->loff.as<const uint32_t>(),
+                c->tiles.as<const uint32_t>(), G, T.t0, T.t1, c->coef.as<uint4>(), c->jsz.as<uint32_t>(),
+                c->joff.as<const uint32_t>(), d_size_out, d_out, cap_out, c->err.as<unsigned long long>());
+}
+
+// The scan and the sizing launch.
+int launch_jpeg_size(myyuv_hip_ctx* c, const FrameGeom& G, const uint8_t* in, const uint32_t* d_size_in,
+                     uint32_t cap_in, hipStream_t s) {
+  const uint32_t ntiles = ceil_div(G.cum[3], kScanTile);
+  unsigned long long* err = c->err.as<unsigned long long>();
+  ScanSrc SS;
+  for (int i = 0; i < 4; i++) SS.cum[i] = G.cum[i];
+  for (int p = 0; p < 3; p++) SS.pos[p] = 0;
+  int e = launch(c, MYYUV_K_SCAN, k_scan_chain, dim3(ntiles, G.nframes), dim3(256), s, in, cap_in, SS, d_size_in,
+                 cap_in, G, c->desc.as<StreamDesc>(), c->loff.as<uint32_t>(), c->tiles.as<uint32_t>(), ntiles,
+                 c->status.as<unsigned long long>(), next_epoch(c), err);
+  e |= launch_jpeg_export(false, c, G, in, d_size_in, cap_in, nullptr, nullptr, 0, s);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+// d_out == nullptr: the files' sizes only.
+int launch_jpeg_place(myyuv_hip_ctx* c, const FrameGeom& G, const myyuv_jpeg::Head& H, uint8_t* d_out,
+                      uint32_t cap_out, uint32_t* d_size_out, hipStream_t s) {
+  const JpegTiles T(G);
+  return launch(c, MYYUV_K_JPEG_PLACE, k_jpeg_place, dim3(G.nframes), dim3(256), s, c->jsz.as<const uint32_t>(),
+                c->joff.as<uint32_t>(), T.t0, T.t1, T.t2, H, d_out, cap_out, d_size_out,
+                c->err.as<unsigned long long>())
+             ? MYYUV_E_HIP
+             : 0;
+}
+
+void jpeg_head(uint32_t w, uint32_t h, const uint8_t q[3], myyuv_jpeg::Head& H) {
+  uint8_t qt[3][64];
+  for (int p = 0; p < 3; p++) {
+    float t[64];
+    make_qtable(q[p], p != 0, t);
+    for (int i = 0; i < 64; i++) qt[p][i] = (uint8_t)t[i];  // integers 1..255
+  }
+  (void)myyuv_jpeg::write_header(H.b, w, h, qt);
+}
+
+int jpeg_dim(uint32_t w, uint32_t h) {
+  return w > myyuv_jpeg::kMaxDim || h > myyuv_jpeg::kMaxDim ? MYYUV_E_JPEG_DIM : 0;
+}
+
+// The host-buffer calls, from the stream on the device (`src`, its size at
+// psize[0], queued on `s`) to the file in `out`.  The file's size comes first
+// (no capacity on the device: the host compares), then a device buffer of
+// that size: none is sized by the bound.
+int jpeg_to_host(myyuv_hip_ctx* c, const FrameGeom& G, uint32_t w, uint32_t h, const uint8_t q[3], const uint8_t* src,
+                 uint32_t cap_in, uint8_t* out, uint32_t cap, uint32_t* out_size, int64_t* bad_block,
+                 hipStream_t s) {
+  myyuv_jpeg::Head H;
+  jpeg_head(w, h, q, H);
+  uint32_t* psz = c->psize.as<uint32_t>();  // [0] the stream's size, [1] the file's
+  int e;
+  if ((e = launch_jpeg_size(c, G, src, psz, cap_in, s)) ||
+      (e = launch_jpeg_place(c, G, H, nullptr, 0xFFFFFFFFu, psz + 1, s)))
+    return e;
+  uint32_t nout = 0;
+  if (hipMemcpyAsync(&nout, psz + 1, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return MYYUV_E_HIP;
+  if ((e = read_err(c, s, bad_block))) {  // (synchronises)
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  *out_size = nout;
+  if (nout > cap) return MYYUV_E_CAPACITY;
+  if (c->jout.grow(((size_t)nout + 3) & ~(size_t)3)) return MYYUV_E_HIP;
+  uint8_t* dst = c->jout.as<uint8_t>();
+  if ((e = launch_jpeg_place(c, G, H, dst, nout, psz + 1, s)) ||
+      (e = launch_jpeg_export(true, c, G, src, psz, cap_in, psz + 1, dst, nout, s)))
+    return e;
+  if (d2h(out, dst, nout, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+}  // namespace
+
+int myyuv_gpu_dct_to_jpeg(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
+                          const uint8_t q[3], uint8_t* out, uint32_t cap, uint32_t* out_size, int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !payload || !out || !out_size || !q) return MYYUV_E_ARG;
+  int e = check_q(q);
+  if (e) return e;
+  FrameGeom G;
+  if ((e = host_parse_headers(payload, size)) || (e = make_geom(w, h, G)) || (e = jpeg_dim(w, h))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const uint32_t cap_in = (size + 3) & ~3u;
+  if ((e = reserve_jpeg(c, G, JpegTiles(G).n()))) return e;
+  if (c->rqsrc.grow(cap_in)) return MYYUV_E_HIP;
+  uint32_t* psz = c->psize.as<uint32_t>();  // [0] the stream's size, [1] the file's
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (hipMemsetAsync(static_cast<uint8_t*>(c->rqsrc.p) + (cap_in - 4), 0, 4, s) != hipSuccess ||
+      h2d(c->rqsrc.p, payload, size, s) || hipMemcpyAsync(psz, &size, 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    return MYYUV_E_HIP;
+  return jpeg_to_host(c, G, w, h, q, c->rqsrc.as<const uint8_t>(), cap_in, out, cap, out_size, bad_block, s);
+}
+
+int myyuv_gpu_iyuv_to_jpeg(myyuv_hip_handle c, const uint8_t* iyuv, uint32_t w, uint32_t h, const uint8_t q[3],
+                           uint8_t* out, uint32_t cap, uint32_t* out_size) {
+  if (!c || !iyuv || !out || !out_size || !q) return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = check_q(q);
+  if (e || (e = make_geom(w, h, G)) || (e = jpeg_dim(w, h))) return e;
+  Entry en(c);
+  hipStream_t s = en.s;
+  const size_t fbytes = (size_t)w * h * 3 / 2;
+  const uint32_t bound = myyuv_dct_payload_bound(w, h);
+  if ((e = reserve(c, G)) || (e = reserve_jpeg(c, G, JpegTiles(G).n())) || (e = set_qtables(c, q, s))) return e;
+  if (c->frame.grow(fbytes) || c->payload.grow(bound)) return MYYUV_E_HIP;
+  if (reset_err(c, s)) return MYYUV_E_HIP;
+  if (h2d(c->frame.p, iyuv, fbytes, s)) return MYYUV_E_HIP;
+  // the stream stays on the device: the encoder's payload buffer is the exporter's source
+  if ((e = launch_compress(c, G, c->frame.p, c->payload.p, bound, c->psize.as<uint32_t>(), s))) return e;
+  return jpeg_to_host(c, G, w, h, q, c->payload.as<const uint8_t>(), bound, out, cap, out_size, nullptr, s);
+}
+
+int myyuv_gpu_dct_to_jpeg_device(myyuv_hip_handle c, const void* d_payload, const uint32_t* d_payload_sizes,
+                                 uint32_t cap_in, uint32_t nframes, uint32_t w, uint32_t h, const uint8_t q[3],
+                                 void* d_out, uint32_t cap_out, uint32_t* d_out_sizes, void* stream) {
+  if (!c || !d_payload || !d_payload_sizes || !d_out || !d_out_sizes || !q) return MYYUV_E_ARG;
+  FrameGeom G;
+  int e = check_q(q);
+  if (e || (e = make_geom(w, h, G)) || (e = set_batch(G, nframes)) || (e = jpeg_dim(w, h))) return e;
+  if (((uintptr_t)d_payload & 3) || (nframes > 1 && (cap_in & 3))) return MYYUV_E_ARG;
+  {  // the two arrays must not overlap: a file is written while later streams are still being read
+    const uintptr_t a = (uintptr_t)d_payload, b = (uintptr_t)d_out;
+    const uint64_t na = (uint64_t)cap_in * nframes, nb = (uint64_t)cap_out * nframes;
+    if (a < b + nb && b < a + na) return MYYUV_E_ARG;
+  }
+  myyuv_jpeg::Head H;
+  jpeg_head(w, h, q, H);
+  Entry en(c, stream);
+  // (as several launches past the kernels' 32-bit block numbers or the grid's 65,535 frames)
+  const uint32_t per = std::min(launch_frames(G, c->launch_blocks), 65535u);
+  FrameGeom GL = G;
+  if ((e = set_batch(GL, std::min(nframes, per))) || (e = reserve_jpeg(c, GL, JpegTiles(G).n()))) return e;
+  for (uint32_t f0 = 0; f0 < nframes; f0 += per) {
+    GL = G;
+    GL.fbase = f0;
+    if ((e = set_batch(GL, std::min(per, nframes - f0)))) return e;
+    const uint8_t* src = static_cast<const uint8_t*>(d_payload) + (size_t)f0 * cap_in;
+    uint8_t* dst = static_cast<uint8_t*>(d_out) + (size_t)f0 * cap_out;
+    if ((e = launch_jpeg_size(c, GL, src, d_payload_sizes + f0, cap_in, en.s)) ||
+        (e = launch_jpeg_place(c, GL, H, dst, cap_out, d_out_sizes + f0, en.s)) ||
+        (e = launch_jpeg_export(true, c, GL, src, d_payload_sizes + f0, cap_in, d_out_sizes + f0, dst, cap_out,
+                                      en.s)))
+      return e;
+  }
+  return 0;
+}
+
 // ---- downscale (defined in myyuv_hip.h) -------------------------------------
 int myyuv_gpu_dct_downscale(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
                             const uint8_t q_src[3], uint32_t denom, const uint8_t q_dst[3], uint8_t* out,
@@ -2709,7 +2899,7 @@ int myyuv_gpu_dct_decompress_to_bmp_frames(myyuv_hip_handle c, const uint8_t* co
 }
 
 int myyuv_hip_profile(myyuv_hip_handle c, int enable) {
-  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_TOP) - 1u : 0u);
+  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_MAX) - 1u : 0u);
 }
 
 int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
@@ -2718,8 +2908,8 @@ int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
   DeviceGuard g(c->device);
   (void)hipStreamSynchronize(c->stream);
   drain_profile(c);
-  c->prof = mask & ((1u << MYYUV_K_TOP) - 1u);
-  for (int k = 0; k < MYYUV_K_TOP; k++) {
+  c->prof = mask & ((1u << MYYUV_K_MAX) - 1u);
+  for (int k = 0; k < MYYUV_K_MAX; k++) {
     c->ms[k] = 0;
     c->launches[k] = 0;
   }
@@ -2732,8 +2922,8 @@ int myyuv_hip_kernel_stats_n(myyuv_hip_handle c, uint32_t n, double* ms, int64_t
   DeviceGuard g(c->device);
   drain_profile(c);
   for (uint32_t k = 0; k < n; k++) {
-    ms[k] = k < MYYUV_K_TOP ? c->ms[k] : 0.0;
-    launches[k] = k < MYYUV_K_TOP ? c->launches[k] : 0;
+    ms[k] = k < MYYUV_K_MAX ? c->ms[k] : 0.0;
+    launches[k] = k < MYYUV_K_MAX ? c->launches[k] : 0;
   }
   return 0;
 }

@@ -48,8 +48,14 @@ K_BOUND = len(KERNELS_FULL)  # MYYUV_K_BOUND: frozen like the bounds before it; 
 # compress-from-BMP's id follows; Codec.profile / Codec.kernel_stats take and return KERNELS_TOP's names
 KERNELS_TOP = KERNELS_FULL + ["bmp_fdct"]
 K_BMP_FDCT = KERNELS_TOP.index("bmp_fdct")
-K_TOP = len(KERNELS_TOP)  # MYYUV_K_TOP
+K_TOP = len(KERNELS_TOP)  # MYYUV_K_TOP: frozen like the bounds before it; the ids after it end at K_MAX
+# the JPEG export's ids follow; Codec.profile / Codec.kernel_stats take and return KERNELS_MAX's names
+KERNELS_MAX = KERNELS_TOP + ["jpeg_export", "jpeg_place"]
+K_JPEG = KERNELS_MAX.index("jpeg_export")
+K_JPEG_PLACE = KERNELS_MAX.index("jpeg_place")
+K_MAX = len(KERNELS_MAX)  # MYYUV_K_MAX
 E_TARGET = 18  # MYYUV_E_TARGET: "target not reachable" (error_message; strerror's table ends at 17)
+E_JPEG_DIM = 20  # MYYUV_E_JPEG_DIM: "JPEG width and height must not exceed 65535" (error_message)
 PROBE_SIZE, PROBE_METRIC = 1, 2  # MYYUV_PROBE_*
 # myyuv_block_metric, as the maps of the compare calls come back
 BLOCK_METRIC = np.dtype([("sse", np.uint32), ("ssim", np.int32)])
@@ -90,6 +96,7 @@ EXPORTS = [
     "myyuv_gpu_dct_compress_to_size", "myyuv_gpu_dct_compress_to_sse",
     "myyuv_gpu_dct_compress_to_size_device", "myyuv_gpu_dct_compress_to_sse_device",
     "myyuv_gpu_bmp_dct_compress", "myyuv_gpu_bmp_dct_compress_device",
+    "myyuv_jpeg_bound", "myyuv_gpu_dct_to_jpeg", "myyuv_gpu_dct_to_jpeg_device", "myyuv_gpu_iyuv_to_jpeg",
 ]
 
 
@@ -260,6 +267,11 @@ def load():
     L.myyuv_gpu_dct_compress_to_sse_device.argtypes = [vp, vp, u32, u32, u64p, vp, u32, vp, trp, vp]
     L.myyuv_gpu_bmp_dct_compress.argtypes = [vp, u8p, i32, i32, u16, u8p, u8p, u32, ctypes.POINTER(u32)]
     L.myyuv_gpu_bmp_dct_compress_device.argtypes = [vp, vp, u32, i32, i32, u16, u8p, vp, u32, vp, vp]
+    L.myyuv_jpeg_bound.argtypes = [u32, u32]
+    L.myyuv_jpeg_bound.restype = ctypes.c_uint64
+    L.myyuv_gpu_dct_to_jpeg.argtypes = [vp, u8p, u32, u32, u32, u8p, u8p, u32, ctypes.POINTER(u32), i64p]
+    L.myyuv_gpu_dct_to_jpeg_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, vp, u32, vp, vp]
+    L.myyuv_gpu_iyuv_to_jpeg.argtypes = [vp, u8p, u32, u32, u8p, u8p, u32, ctypes.POINTER(u32)]
     L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -281,6 +293,11 @@ def error_message(code):
 
 def payload_bound(w, h):
     return load().myyuv_dct_payload_bound(w, h)
+
+
+def jpeg_bound(w, h):
+    """myyuv_jpeg_bound: a size no exported file of a w x h frame exceeds."""
+    return int(load().myyuv_jpeg_bound(w, h))
 
 
 def metric_psnr(sse, nsamples):
@@ -873,6 +890,69 @@ class Codec:
         if rc:
             raise CodecError(rc)
 
+    # -- export to JPEG: a DCT stream written as a baseline JPEG file on its
+    # coefficients (defined in include/myyuv_hip.h) --
+    def to_jpeg(self, payload, w, h, q):
+        """DCTYUV payload written at q -> the JPEG file's bytes.  The first try
+        has room for a file of the stream's size (a picture's file is about
+        half of it); a larger file is asked for again at the size the call
+        reports, never at jpeg_bound."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(payload).cast("B"), np.uint8))
+        out = np.empty(src.nbytes + 1024, np.uint8)
+        try:
+            n = self.to_jpeg_into(src, w, h, q, out)
+        except CodecError as e:
+            if e.code != E_CAPACITY:
+                raise
+            out = np.empty(e.size, np.uint8)
+            n = self.to_jpeg_into(src, w, h, q, out)
+        return out[:n].tobytes()
+
+    def to_jpeg_into(self, payload, w, h, q, out):
+        """to_jpeg from / into the caller's C-contiguous uint8 arrays, which
+        must not overlap; returns the file's size.  `out` is sized by its byte
+        count; a short one fails with E_CAPACITY, the error's .size the size
+        needed."""
+        src = _u8_array(payload, "payload")
+        dst = _u8_array(out, "out", writable=True)
+        size = ctypes.c_uint32(0)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_dct_to_jpeg(self._h, _u8(src), src.nbytes, w, h, _u8(_q(q)), _u8(dst), dst.nbytes,
+                                          ctypes.byref(size), ctypes.byref(bad))
+        if rc:
+            e = CodecError(rc, bad.value)
+            e.size = size.value
+            raise e
+        return size.value
+
+    def iyuv_to_jpeg(self, iyuv, w, h, q):
+        """Raw IYUV frame -> the JPEG file of its stream at q (compress, then
+        to_jpeg; the stream stays on the device)."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(iyuv).cast("B"), np.uint8))
+        if src.size < w * h * 3 // 2:
+            raise ValueError("frame smaller than W*H*3/2")
+        size = ctypes.c_uint32(0)
+        out = np.empty(max(4096, w * h // 4), np.uint8)
+        for _ in range(2):
+            rc = load().myyuv_gpu_iyuv_to_jpeg(self._h, _u8(src), w, h, _u8(_q(q)), _u8(out), out.nbytes,
+                                               ctypes.byref(size))
+            if rc != E_CAPACITY:
+                break
+            out = np.empty(size.value, np.uint8)
+        if rc:
+            raise CodecError(rc)
+        return out[:size.value].tobytes()
+
+    def to_jpeg_device(self, d_payload, d_sizes, cap_in, nframes, w, h, q, d_out, cap_out, d_out_sizes,
+                       stream=None):
+        """Device-resident batch: stream f at d_payload + f*cap_in (size
+        d_sizes[f]) -> the file at d_out + f*cap_out, its size at
+        d_out_sizes[f] (device u32); asynchronous, errors through sync_status."""
+        rc = load().myyuv_gpu_dct_to_jpeg_device(self._h, d_payload, d_sizes, cap_in, nframes, w, h, _u8(_q(q)),
+                                                 d_out, cap_out, d_out_sizes, stream)
+        if rc:
+            raise CodecError(rc)
+
     # -- transform: a DCT stream mirrored, rotated or transposed on its coefficients,
     # optionally at another quality (defined in include/myyuv_hip.h) --
     def transform(self, payload, w, h, q_src, op, q_dst=None):
@@ -1066,19 +1146,19 @@ class Codec:
         if kernels is None:
             rc = load().myyuv_hip_profile(self._h, 1 if enable else 0)
         else:
-            mask = sum(1 << KERNELS_TOP.index(k) for k in kernels) if enable else 0
+            mask = sum(1 << KERNELS_MAX.index(k) for k in kernels) if enable else 0
             rc = load().myyuv_hip_profile_kernels(self._h, mask)
         if rc:
             raise CodecError(rc)
 
     def kernel_stats(self):
-        """{name: (summed ms, launches)} for every name of KERNELS_TOP."""
-        ms = (ctypes.c_double * K_TOP)()
-        n = (ctypes.c_int64 * K_TOP)()
-        rc = load().myyuv_hip_kernel_stats_n(self._h, K_TOP, ms, n)
+        """{name: (summed ms, launches)} for every name of KERNELS_MAX."""
+        ms = (ctypes.c_double * K_MAX)()
+        n = (ctypes.c_int64 * K_MAX)()
+        rc = load().myyuv_hip_kernel_stats_n(self._h, K_MAX, ms, n)
         if rc:
             raise CodecError(rc)
-        return {KERNELS_TOP[i]: (ms[i], n[i]) for i in range(K_TOP)}
+        return {KERNELS_MAX[i]: (ms[i], n[i]) for i in range(K_MAX)}
 
     def tinfo_guard(self, ntiles, arm):
         """Diagnostic (not in include/myyuv_hip.h): arm=True writes a canary
