@@ -1005,6 +1005,133 @@ int myyuv_gpu_dct_to_jpeg_device(myyuv_hip_handle h, const void* d_payload, cons
                                  const uint8_t quality[3], void* d_out, uint32_t cap_out, uint32_t* d_out_sizes,
                                  void* stream);
 
+/* Import from JPEG: a baseline 4:2:0 JPEG file read into a DCT stream on its
+ * coefficients — the way IN, the reverse of the export above.  The codec is
+ * baseline JPEG in all but its entropy coder and its container, so a file's
+ * quantised coefficients are a stream's: the file's Huffman code is decoded on
+ * the GPU, no transform runs, and with the file's own tables kept nothing is
+ * rounded again.  No reference program does this, so the definition is stated
+ * here, bit for bit.
+ *
+ * Accepted files run SOI ... EOI (bytes after EOI are ignored) and hold
+ *   - exactly one frame, SOF0, precision 8, three components with sampling
+ *     factors (2,2), (1,1), (1,1) in this order (component ids are free),
+ *     width and height 1..65535;
+ *   - 8-bit quantisation tables (Pq 0, entries 1..255) and Huffman tables,
+ *     each defined before the scan that uses it (a later definition of the
+ *     same slot serves the later scans; several tables in one segment are
+ *     fine);
+ *   - either ONE interleaved scan (Ns 3, the components in frame order): MCU =
+ *     Y00 Y01 Y10 Y11 Cb Cr, MCUs in raster order over the ceil(W/16) x
+ *     ceil(H/16) grid (what cameras and libjpeg write), or THREE
+ *     non-interleaved scans (Ns 1) in any component order: MCU = one block, in
+ *     raster order over the component's own ceil(W/8) x ceil(H/8) (luma) or
+ *     ceil(W/16) x ceil(H/16) (chroma) blocks (what the export above writes);
+ *     every scan Ss 0, Se 63, Ah/Al 0;
+ *   - DRI of any value, none and 0 included, and it may change between scans;
+ *   - APPn and COM segments, which are skipped (JFIF, EXIF and ICC are not
+ *     carried over), and fill bytes (repeated 0xFF) before any marker.
+ * What baseline allows but the container cannot hold is
+ * MYYUV_E_JPEG_UNSUPPORTED: SOF1-3 and SOF5-15 (and DAC), a component count
+ * other than 3, any other sampling, 16-bit tables, DNL (or a frame height of
+ * 0), a second frame, a scan of two components, an Adobe APP14 segment whose
+ * transform is not 1.  Structural damage is MYYUV_E_JPEG_SYNTAX: no SOI, a
+ * truncated segment, a table entry of 0, BITS that oversubscribe the code
+ * space or name more than 256 symbols, no SOF before SOS, a scan naming an
+ * undefined table or component or not Ss 0 / Se 63 / Ah/Al 0, a component
+ * covered twice or not at all, a restart count other than ceil(MCUs / Ri) - 1,
+ * an RSTm out of sequence (m counts 0..7 from 0 in every scan), a missing EOI.
+ * The first such finding in file order is the one reported.
+ *
+ * The frame.  The stream's frame is Wp x Hp, Wp = 16 ceil(W/16), Hp = 16
+ * ceil(H/16): the file's own MCU-padded block grid, so every block of the file
+ * is the stream's block at the same position.  Pixels beyond W x H are
+ * whatever the file's encoder padded with.  Blocks of the grid that no scan
+ * holds (non-interleaved scans of a picture whose last MCU column or row is
+ * half empty) are all-zero.  Wp and Hp beyond what a stream's frame may be
+ * are reported as myyuv_gpu_dct_compress reports them.
+ *
+ * The coefficients.  Within a restart interval (the whole scan where Ri = 0),
+ * per ITU-T T.81 F.2.2: DC = predictor + EXTEND(value), the predictor per
+ * component and 0 at every interval's start; AC by run/size with ZRL and EOB;
+ * zig-zag positions to natural ones by the export's table.  These are errors,
+ * MYYUV_E_JPEG_DATA with *bad_block the lowest failing block's index in the
+ * stream's block order (Y raster, then U, then V): a DC category above 11, a
+ * DC outside [-1024, 1023], an AC size of 0 with a run other than 0 or 15, an
+ * AC size above 10, a run (or a ZRL, after which a coefficient must follow)
+ * that passes position 63, a bit pattern that is no code of the table, a block
+ * that needs bits beyond its interval's last byte.  The failing block and the
+ * rest of its interval count as all-zero; the stream's bytes are then
+ * unspecified but stay inside `cap` (the export's rule for a bad block,
+ * mirrored).  Bytes or bits left over at an interval's end are ignored, as
+ * libjpeg does.
+ *
+ * The quality.  quality == NULL means KEEP: each plane's table must equal
+ * make_qtable(q, p != 0) for some q in 1..100, the plane takes the smallest
+ * such q (the luma map q -> table is injective; the chroma one coincides only
+ * for q = 1, 2, 3, all entries 255) and the coefficients pass through
+ * unchanged; a plane with no such q is MYYUV_E_JPEG_TABLES.  With `quality`
+ * (each 1..100, else MYYUV_E_QUALITY) every coefficient z of plane p becomes
+ * myyuv_requant::requant_coef(z, Qfile[n], make_qtable(quality[p])[n])
+ * (csrc/requant.h: one more rounding, as requantise adds; a plane whose table
+ * is already the destination's passes through bit-exact).  q_out[3] are the
+ * qualities the stream is to be decoded with.
+ *
+ * The stream is what K2 and the stream writer emit for those coefficients,
+ * byte for byte: for a file the export wrote from an encoder-written stream s,
+ * import(export(s)) is s, with the qualities export was given (1 for a chroma
+ * quality of 1..3).
+ *
+ * How it runs (part of the contract, MYYUV_JPEG_SEGMENTS_MIN = 64): a file
+ * whose scans have at least 64 restart intervals in all, none of them without
+ * a restart interval, is decoded on the GPU, one lane per interval; any other
+ * file is Huffman-decoded on the host by the same code (csrc/jpeg_import.h)
+ * and its coefficient image uploaded.  Both give the same stream.
+ *
+ * myyuv_jpeg_inspect needs no handle and no device: it walks the markers and
+ * reports the sizes, the layout and, per plane, the quality KEEP would take
+ * (0: none).  payload_bound is myyuv_dct_payload_bound(Wp, Hp), 0 when the
+ * frame is beyond a stream's.
+ * Checks of myyuv_gpu_jpeg_to_dct, in order: pointers (MYYUV_E_ARG; quality
+ * and bad_block may be NULL), the file (UNSUPPORTED / SYNTAX in file order),
+ * the quality (MYYUV_E_QUALITY, or MYYUV_E_JPEG_TABLES for KEEP), the frame,
+ * the data, the capacity: a stream larger than `cap` is MYYUV_E_CAPACITY with
+ * *out_size the size needed, and nothing is written.  *width and *height are
+ * Wp and Hp (myyuv_jpeg_inspect has W and H).
+ * The device form takes the same file twice: `d_file` on the device (4-byte
+ * aligned, readable to size rounded up to 4) for the kernel, and `file`, the
+ * same bytes on the host, which the call parses itself, so no table it did not
+ * check reaches the kernel.  It is asynchronous on `stream` (NULL = the
+ * context's), takes the restart-interval path only (a file below the
+ * threshold is MYYUV_E_JPEG_UNSUPPORTED here) and reports data errors and a
+ * stream larger than `cap` through myyuv_hip_sync_status; the stream goes to
+ * d_out (4-byte aligned), its size to *d_out_size.
+ * Workspace: the compress calls', the segment table (20 B per interval), the
+ * Huffman tables and the file or the coefficient image (128 B per block). */
+#define MYYUV_E_JPEG_UNSUPPORTED 21 /* "JPEG file is not a baseline 4:2:0 picture the container can hold" */
+#define MYYUV_E_JPEG_SYNTAX 22      /* "JPEG file is damaged" */
+#define MYYUV_E_JPEG_DATA 23        /* "JPEG entropy data is damaged" */
+#define MYYUV_E_JPEG_TABLES 24      /* "the file's tables are not the codec's: name a quality" */
+#define MYYUV_JPEG_SEGMENTS_MIN 64
+typedef struct myyuv_jpeg_info {
+  uint32_t width, height;               /* the file's W x H */
+  uint32_t padded_width, padded_height; /* the stream's Wp x Hp */
+  uint32_t scans;                       /* 1 (interleaved) or 3 */
+  uint32_t restart_interval[3];         /* Ri of scan s, in MCUs (0: none) */
+  uint32_t segments;                    /* restart intervals of all scans */
+  uint32_t on_gpu;                      /* 1: the restart-interval path applies */
+  uint32_t payload_bound;
+  uint8_t keep_quality[3];              /* per plane, 0: none */
+  uint8_t reserved;
+} myyuv_jpeg_info;
+int myyuv_jpeg_inspect(const uint8_t* file, uint32_t size, myyuv_jpeg_info* info);
+int myyuv_gpu_jpeg_to_dct(myyuv_hip_handle h, const uint8_t* file, uint32_t size, const uint8_t* quality,
+                          uint8_t* out, uint32_t cap, uint32_t* out_size, uint32_t* width, uint32_t* height,
+                          uint8_t q_out[3], int64_t* bad_block);
+int myyuv_gpu_jpeg_to_dct_device(myyuv_hip_handle h, const void* d_file, const uint8_t* file, uint32_t size,
+                                 const uint8_t* quality, void* d_out, uint32_t cap, uint32_t* d_out_size,
+                                 uint32_t* width, uint32_t* height, uint8_t q_out[3], void* stream);
+
 /* Host-buffer batches (many frames per call; §7 step 9:
  * transfers overlapped with the kernels).  The batch runs in chunks of up to
  * 8 frames through two device slots: chunk k's host -> device copies, chunk
@@ -1111,7 +1238,14 @@ int myyuv_hip_sync_status(myyuv_hip_handle h, void* stream, int64_t* bad_block);
  * of them. */
 #define MYYUV_K_JPEG 25      /* decode + baseline entropy coder of the JPEG export, both launches (jpeg_export) */
 #define MYYUV_K_JPEG_PLACE 26 /* the export's interval offsets, file header and markers (jpeg_place) */
-#define MYYUV_K_MAX 27       /* every id is below this */
+#define MYYUV_K_MAX 27       /* every id above is below this */
+/* MYYUV_K_MAX is frozen as the bounds before it (callers size their arrays
+ * with it too).  The ids of the JPEG import follow it; MYYUV_K_CEIL is the
+ * bound of all ids, and the length to pass to myyuv_hip_kernel_stats_n for all
+ * of them. */
+#define MYYUV_K_JPEG_IMPORT 27      /* baseline Huffman decoder of the JPEG import, a lane per restart interval (jpeg_import) */
+#define MYYUV_K_JPEG_IMPORT_COEF 28 /* the import's hand-off from a host-decoded coefficient image (jpeg_import_coef) */
+#define MYYUV_K_CEIL 29       /* every id is below this */
 int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 /* As myyuv_hip_profile, but stamps only the kernels whose bit (1 << MYYUV_K_*)
  * is set in `mask` (0 disables): event stamping costs host and queue time per
@@ -1119,8 +1253,8 @@ int myyuv_hip_profile(myyuv_hip_handle h, int enable);
 int myyuv_hip_profile_kernels(myyuv_hip_handle h, uint32_t mask);
 int myyuv_hip_kernel_stats(myyuv_hip_handle h, double ms[MYYUV_K_COUNT],
                            int64_t launches[MYYUV_K_COUNT]);
-/* The same for the first min(n, MYYUV_K_MAX) ids; entries from
- * MYYUV_K_MAX on, if any, are set to 0. */
+/* The same for the first min(n, MYYUV_K_CEIL) ids; entries from
+ * MYYUV_K_CEIL on, if any, are set to 0. */
 int myyuv_hip_kernel_stats_n(myyuv_hip_handle h, uint32_t n, double* ms, int64_t* launches);
 
 /* Block-level entry points for known-answer tests (device round trip of one

@@ -35,6 +35,10 @@
 // device:
 //   myyuv_cli in.myyuv -to_jpeg -o out.jpg
 //   myyuv_cli raw.myyuv -to_jpeg -q q [q [q]] -o out.jpg
+// a baseline 4:2:0 JPEG file read into a compressed image on its coefficients
+// (import from JPEG, include/myyuv_hip.h; -q: rescaled to those qualities,
+// otherwise the file's tables are kept and must be a quality's):
+//   myyuv_cli in.jpg -from_jpeg [-q q [q [q]]] -o out.myyuv
 // a compressed input mirrored, rotated or transposed on its coefficients
 // (transform, include/myyuv_hip.h; -q: re-encoded at those qualities on the
 // way, otherwise at its own):
@@ -109,6 +113,9 @@ void usage() {
             << "  myyuv_cli IMAGE.myyuv -to_jpeg [-q Q [Q [Q]]] -o OUT.jpg\n"
             << "      (a baseline JPEG straight from a compressed image's DCT coefficients; -q: an uncompressed\n"
             << "       image, compressed at those qualities and exported on the GPU)\n"
+            << "  myyuv_cli IMAGE.jpg -from_jpeg [-q Q [Q [Q]]] -o OUT.myyuv\n"
+            << "      (a compressed image straight from a baseline 4:2:0 JPEG's DCT coefficients; -q: rescaled to\n"
+            << "       those qualities, otherwise the file's own tables are kept)\n"
             << "  myyuv_cli IMAGE.myyuv -transform flip_h|flip_v|rot180|transpose|transverse|rot90|rot270"
                " [-q Q [Q [Q]]] -o OUT.myyuv\n"
             << "      (a compressed image mirrored, rotated or transposed, straight from its DCT coefficients)\n"
@@ -854,6 +861,41 @@ int run_join(const std::vector<std::string>& args) {
   return 0;
 }
 
+// IMAGE.jpg -from_jpeg [-q Q [Q [Q]]] -o OUT.myyuv: the qualities as -compress DCT's
+int run_jpeg(const std::string& path, const std::vector<std::string>& args) {
+  size_t a = 2;
+  if (args[a] != "-from_jpeg") {
+    std::cout << "Invalid argument, a JPEG image takes `-from_jpeg` only\n";
+    usage();
+    return 1;
+  }
+  a++;
+  const bool with_q = a < args.size() && args[a] == "-q";
+  std::vector<std::string> params;
+  if (with_q) a++;
+  while (a < args.size() && args[a] != "-o") params.push_back(args[a++]);
+  a++;
+  if (a >= args.size() || args.size() != a + 1 || (!with_q && !params.empty())) {
+    std::cout << "Invalid argument, last arguments must be `-o /path/to/new_image.myyuv`\n";
+    usage();
+    return 1;
+  }
+  uint8_t q[3];
+  if (with_q) dct_qualities(params, q);
+  std::ifstream f(path, std::ios::binary);
+  const std::vector<uint8_t> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  if (!f && !f.eof()) throw std::runtime_error("Error reading " + path);
+  myyuv::YUV out;
+  myyuv_jpeg_info info;
+  const float ms = elapsed_ms([&] { out = myyuv::YUV::from_jpeg(file, with_q ? q : nullptr, &info); });
+  std::cout << "JPEG to YUV DCT : " << ms << " ms\n";
+  if (info.width != info.padded_width || info.height != info.padded_height)
+    std::cout << "Notice: " << info.width << "x" << info.height << " padded to " << info.padded_width << "x"
+              << info.padded_height << " (the file's own MCU grid)\n";
+  out.dump(args[a]);
+  return 0;
+}
+
 int run(int argc, char* argv[]) {
   if (argc <= 2) {
     usage();
@@ -882,6 +924,8 @@ int run(int argc, char* argv[]) {
     rc = run_yuv(myyuv::YUV(path), 2, args);
   } else if (magic[0] == 'B' && magic[1] == 'M') {
     rc = run_bmp(myyuv::BMP(path), 2, args);
+  } else if ((uint8_t)magic[0] == 0xFF && (uint8_t)magic[1] == 0xD8) {
+    rc = run_jpeg(path, args);
   } else {
     throw std::runtime_error("Unknown image format (magic) " + path);
   }

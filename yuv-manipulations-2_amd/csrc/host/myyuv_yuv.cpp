@@ -575,6 +575,37 @@ std::vector<uint8_t> YUV::to_jpeg(const std::array<uint8_t, 3>& q) const {
   });
 }
 
+YUV YUV::from_jpeg(const std::vector<uint8_t>& file, const uint8_t* q, myyuv_jpeg_info* info) {
+  // the file's checks need no device: they come first
+  myyuv_jpeg_info I;
+  int rc = myyuv_jpeg_inspect(file.data(), (uint32_t)file.size(), &I);
+  if (rc) fail(rc);
+  if (info) *info = I;
+  if (q)
+    for (int p = 0; p < 3; p++)
+      if (q[p] < 1 || q[p] > 100) throw std::runtime_error("Level of quality must be between 1 and 100");
+  std::vector<uint8_t> payload(I.payload_bound ? I.payload_bound : 64);
+  uint32_t size = 0, w = 0, h = 0;
+  uint8_t qs[3] = {0, 0, 0};
+  int64_t bad = -1;
+  rc = myyuv_gpu_jpeg_to_dct(t_codec.get(), file.data(), (uint32_t)file.size(), q, payload.data(),
+                             (uint32_t)payload.size(), &size, &w, &h, qs, &bad);
+  if (rc) fail(rc);
+  YUV res;
+  res.header.fourcc_format = FourccFormats::IYUV;
+  res.header.width = w;
+  res.header.height = h;
+  res.header.compression = Compressions::DCT;
+  res.header.compression_params_size = 3;
+  res.header.compression_params_pos = sizeof(YUVHeader);
+  res.header.data_pos = sizeof(YUVHeader) + 3;
+  res.header.data_size = size;
+  res.compression_params = new uint8_t[3]{qs[0], qs[1], qs[2]};
+  res.data = new uint8_t[size];
+  std::memcpy(res.data, payload.data(), size);
+  return res;
+}
+
 }  // namespace myyuv
 
 namespace myyuvDCT {

@@ -122,6 +122,13 @@ class YUV {
   // the file of compress at q, the stream never leaving the device.
   std::vector<uint8_t> to_jpeg() const;
   std::vector<uint8_t> to_jpeg(const std::array<uint8_t, 3>& q) const;
+  // Import from JPEG (include/myyuv_hip.h): the DCT-compressed planar frame
+  // of a baseline 4:2:0 JPEG file's coefficients, Wp x Hp (the file's
+  // MCU-padded grid).  q null: the file's tables are kept (they must be a
+  // quality's); else three qualities the coefficients are rescaled to.  A file
+  // the import refuses: std::runtime_error with myyuv_hip_error_message's text,
+  // before any device is touched.  info, if given: myyuv_jpeg_inspect's.
+  static YUV from_jpeg(const std::vector<uint8_t>& file, const uint8_t* q = nullptr, myyuv_jpeg_info* info = nullptr);
   void load(const std::string& path);
   void load(const BMP& bmp, FourccFormat format);
   void dump(const std::string& path) const;

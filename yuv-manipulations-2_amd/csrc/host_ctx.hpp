@@ -18,6 +18,7 @@
 #include "codec_common.hpp"
 #include "downscale.h"
 #include "jpeg_export.h"
+#include "jpeg_import.h"
 #include "k_chain.hpp"
 #include "k_stream.hpp"
 #include "myyuv_hip.h"
@@ -59,6 +60,11 @@ __global__ void k_jpeg_export(const uint8_t*, const uint32_t*, uint32_t, const S
                               const uint32_t*, uint8_t*, uint32_t, unsigned long long*);
 __global__ void k_jpeg_place(const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, myyuv_jpeg::Head, uint8_t*,
                              uint32_t, uint32_t*, unsigned long long*);
+__global__ void k_jpeg_import(const uint32_t*, const myyuv_jpegin::Seg*, uint32_t, myyuv_jpegin::Plan,
+                              const myyuv_jpegin::DecTab*, const RequantTables*, uint32_t, uint4*, uint8_t*, uint32_t*,
+                              unsigned long long*);
+__global__ void k_jpeg_import_coef(const uint4*, uint32_t, uint32_t, uint32_t, const RequantTables*, uint32_t, uint4*,
+                                   uint8_t*, uint32_t*);
 template <uint32_t W>
 __global__ void k_huff_encode(const uint4*, const uint32_t*, const uint4*, FrameGeom, uint32_t*, uint32_t*,
                               uint8_t*, uint32_t*, uint32_t*, uint32_t*);
@@ -266,6 +272,9 @@ struct myyuv_hip_ctx {
   // export to JPEG: per 64-block group the interval's size (the sizing
   // launch) and its file offset (k_jpeg_place); the host-buffer calls' file
   DevBuf jsz, joff, jout;
+  // import from JPEG: the file (or the host-decoded coefficient image), the
+  // segment table, the six decode tables and the call's rescale tables
+  DevBuf jin, jseg, jtab, jrq;
   // profiling: the kernels' start/stop events until drain_profile reads
   // them; they are used again from launch to launch
   struct Stamp {
@@ -274,8 +283,8 @@ struct myyuv_hip_ctx {
   };
   uint32_t prof = 0;  // bit k: stamp kernel id k
   uint32_t skip = 0;  // diagnostic: bit k: do not launch kernel id k (myyuv_debug_skip_kernels)
-  double ms[MYYUV_K_MAX] = {};
-  int64_t launches[MYYUV_K_MAX] = {};
+  double ms[MYYUV_K_CEIL] = {};
+  int64_t launches[MYYUV_K_CEIL] = {};
   std::vector<Stamp> pending;
   std::vector<Event> free_events;
   // set once every piece of it exists (pipe_init)

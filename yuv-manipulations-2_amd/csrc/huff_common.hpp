@@ -6,6 +6,7 @@
 // product; the host build is test infrastructure.
 #pragma once
 #include "codec_common.hpp"
+#include "requant.h"
 
 #define MYYUV_HD __host__ __device__ __forceinline__
 
@@ -683,6 +684,39 @@ __device__ __forceinline__ void block_class_msz(const CoefRegs& R, int& msz, uin
 MYYUV_HD void block_class_msz(const CoefRegs& R, int& msz, uint32_t& cls) {
   msz = R.msz();
   cls = block_class(R, msz);
+}
+#endif
+
+#if defined(__HIPCC__)
+// The tail k_requant and the JPEG import's kernels share: block g's 64
+// coefficients in R's natural-order words are rescaled from the table qs to
+// the table qd (requant.h; `rescale` false: they pass through; an all-zero row
+// stays zero and is skipped) and written as K1's hand-off for K2: the nonzero
+// rows as natural-order quads, the row mask and the block's info word, with
+// msz and the class of the block as written.
+__device__ __forceinline__ void requant_handoff(CoefRegs& R, uint32_t g, bool rescale, const float* qs,
+                                                const float* qd, uint4* __restrict__ coef,
+                                                uint8_t* __restrict__ rmask, uint32_t* __restrict__ binfo) {
+  uint32_t(&nw)[32] = R.w;
+  uint32_t m = 0;
+#pragma unroll
+  for (int c = 0; c < 8; c++) {
+    if (rescale && (nw[4 * c] | nw[4 * c + 1] | nw[4 * c + 2] | nw[4 * c + 3]) != 0u) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int n = 8 * c + 2 * k;  // coefficients n, n + 1 of the block
+        nw[4 * c + k] = myyuv_requant::requant_word(nw[4 * c + k], qs[n], qs[n + 1], qd[n], qd[n + 1]);
+      }
+    }
+    const bool nz = (nw[4 * c] | nw[4 * c + 1] | nw[4 * c + 2] | nw[4 * c + 3]) != 0u;
+    m |= nz ? 1u << c : 0u;
+    if (nz) coef[coef_quad(g, c)] = make_uint4(nw[4 * c], nw[4 * c + 1], nw[4 * c + 2], nw[4 * c + 3]);
+  }
+  int msz;
+  uint32_t cls;
+  block_class_msz(R, msz, cls);
+  rmask[g] = (uint8_t)m;
+  binfo[g] = binfo_word(m, (uint32_t)msz, cls, nw[0] & 0xFFFFu);
 }
 #endif
 

@@ -1749,25 +1749,7 @@ __global__ __launch_bounds__(64, MYYUV_K5_WAVES) void k_requant(const uint8_t* _
   }
 #pragma unroll
   for (int w = 0; w < 32; w++) nw[w] = keep ? nw[w] : 0u;
-  uint32_t m = 0;
-#pragma unroll
-  for (int c = 0; c < 8; c++) {
-    if ((nw[4 * c] | nw[4 * c + 1] | nw[4 * c + 2] | nw[4 * c + 3]) != 0u) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int n = 8 * c + 2 * k;  // coefficients n, n + 1 of the block
-        nw[4 * c + k] = myyuv_requant::requant_word(nw[4 * c + k], sqs[n], sqs[n + 1], sqd[n], sqd[n + 1]);
-      }
-    }
-    const bool nz = (nw[4 * c] | nw[4 * c + 1] | nw[4 * c + 2] | nw[4 * c + 3]) != 0u;
-    m |= nz ? 1u << c : 0u;
-    if (nz) coef[coef_quad(g, c)] = make_uint4(nw[4 * c], nw[4 * c + 1], nw[4 * c + 2], nw[4 * c + 3]);
-  }
-  int msz;
-  uint32_t cls;
-  block_class_msz(R, msz, cls);
-  rmask[g] = (uint8_t)m;
-  binfo[g] = binfo_word(m, (uint32_t)msz, cls, nw[0] & 0xFFFFu);
+  requant_handoff(R, g, true, sqs, sqd, coef, rmask, binfo);
 }
 
 // ---- transform ------------------------------------------------------------

@@ -567,6 +567,26 @@ int set_requant_tables(myyuv_hip_ctx* c, const uint8_t qs[3], const uint8_t qd[3
   return 0;
 }
 
+// The encoder from K2 on, over K1's hand-off (coefficient quads, row masks,
+// block words) of Gd's batch: K2, the tile scan and the stream writer, as
+// launch_compress runs them after K1.  Shared by requantise, transform,
+// downscale and the JPEG import; the caller has zeroed work[0].
+int launch_encode_tail(myyuv_hip_ctx* c, const FrameGeom& Gd, void* d_out, uint32_t cap_out, uint32_t* d_size_out,
+                       hipStream_t s) {
+  const uint32_t nf = Gd.nframes;
+  unsigned long long* err = c->err.as<unsigned long long>();
+  int e = 0;
+  e |= launch_huff_encode(c, Gd, s);
+  e |= launch(c, MYYUV_K_SCAN, k_tile_scan, dim3(nf), dim3(256), s, c->tinfo.as<uint32_t>(), Gd,
+              static_cast<uint8_t*>(d_out), cap_out, d_size_out, err);
+  const uint32_t W = k2_win(nf * Gd.tcum[3]);  // (K2's windows, as launch_compress)
+  e |= launch(c, MYYUV_K_COMPACT, k_stream_out, dim3(ceil_div(Gd.tcum[3] * nf, 8 * W) * 8 * W), dim3(256), s,
+              c->stage.as<const uint32_t>(), c->tinfo.as<const uint32_t>(), c->sizes.as<const uint8_t>(),
+              c->srcoff.as<const uint32_t>(), c->oslots.as<const uint32_t>(), Gd, static_cast<uint8_t*>(d_out),
+              cap_out, W);
+  return e ? MYYUV_E_HIP : 0;
+}
+
 // Requantise and transform (include/myyuv_hip.h): stream f at d_in + f * cap_in
 // (its size at d_size_in[f]) -> stream f at d_out + f * cap_out, its size at
 // d_size_out[f].  The scan as launch_decompress runs it; k_requant (op < 0) or
@@ -607,14 +627,7 @@ int launch_recode(myyuv_hip_ctx* c, const FrameGeom& G, const FrameGeom& Gd, int
                 (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, t0, t1,
                 c->rqt.as<const RequantTables>(), (uint32_t)op, c->rq_eq, c->xfgen.as<uint4>(), c->coef.as<uint4>(),
                 c->rmask.as<uint8_t>(), c->binfo.as<uint32_t>(), err);
-  e |= launch_huff_encode(c, Gd, s);
-  e |= launch(c, MYYUV_K_SCAN, k_tile_scan, dim3(nf), dim3(256), s, c->tinfo.as<uint32_t>(), Gd,
-              static_cast<uint8_t*>(d_out), cap_out, d_size_out, err);
-  const uint32_t W = k2_win(nf * Gd.tcum[3]);  // (K2's windows, as launch_compress)
-  e |= launch(c, MYYUV_K_COMPACT, k_stream_out, dim3(ceil_div(Gd.tcum[3] * nf, 8 * W) * 8 * W), dim3(256), s,
-              c->stage.as<const uint32_t>(), c->tinfo.as<const uint32_t>(), c->sizes.as<const uint8_t>(),
-              c->srcoff.as<const uint32_t>(), c->oslots.as<const uint32_t>(), Gd, static_cast<uint8_t*>(d_out),
-              cap_out, W);
+  e |= launch_encode_tail(c, Gd, d_out, cap_out, d_size_out, s);
   return e ? MYYUV_E_HIP : 0;
 }
 
@@ -690,14 +703,7 @@ int launch_downscale(myyuv_hip_ctx* c, const FrameGeom& G, const FrameGeom& Gd, 
               (const StreamDesc*)desc, c->loff.as<const uint32_t>(), c->tiles.as<const uint32_t>(), G, Gd, M,
               c->dst.as<const DownscaleTables>(), c->coef.as<uint4>(), c->rmask.as<uint8_t>(),
               c->binfo.as<uint32_t>(), err);
-  e |= launch_huff_encode(c, Gd, s);
-  e |= launch(c, MYYUV_K_SCAN, k_tile_scan, dim3(nf), dim3(256), s, c->tinfo.as<uint32_t>(), Gd,
-              static_cast<uint8_t*>(d_out), cap_out, d_size_out, err);
-  const uint32_t W = k2_win(nf * Gd.tcum[3]);  // (K2's windows, as launch_compress)
-  e |= launch(c, MYYUV_K_COMPACT, k_stream_out, dim3(ceil_div(Gd.tcum[3] * nf, 8 * W) * 8 * W), dim3(256), s,
-              c->stage.as<const uint32_t>(), c->tinfo.as<const uint32_t>(), c->sizes.as<const uint8_t>(),
-              c->srcoff.as<const uint32_t>(), c->oslots.as<const uint32_t>(), Gd, static_cast<uint8_t*>(d_out),
-              cap_out, W);
+  e |= launch_encode_tail(c, Gd, d_out, cap_out, d_size_out, s);
   return e ? MYYUV_E_HIP : 0;
 }
 
@@ -841,6 +847,10 @@ const char* myyuv_hip_strerror(int code) {
 const char* myyuv_hip_error_message(int code) {
   if (code == MYYUV_E_TARGET) return "target not reachable";
   if (code == MYYUV_E_JPEG_DIM) return "JPEG width and height must not exceed 65535";
+  if (code == MYYUV_E_JPEG_UNSUPPORTED) return "JPEG file is not a baseline 4:2:0 picture the container can hold";
+  if (code == MYYUV_E_JPEG_SYNTAX) return "JPEG file is damaged";
+  if (code == MYYUV_E_JPEG_DATA) return "JPEG entropy data is damaged";
+  if (code == MYYUV_E_JPEG_TABLES) return "the file's tables are not the codec's: name a quality";
   return myyuv_hip_strerror(code);
 }
 
@@ -2282,6 +2292,208 @@ int myyuv_gpu_dct_to_jpeg_device(myyuv_hip_handle c, const void* d_payload, cons
   return 0;
 }
 
+// ---- import from JPEG (defined in myyuv_hip.h) ------------------------------
+static_assert(MYYUV_E_JPEG_UNSUPPORTED == myyuv_jpegin::kUnsupported && MYYUV_E_JPEG_SYNTAX == myyuv_jpegin::kSyntax &&
+                  MYYUV_E_JPEG_DATA == myyuv_jpegin::kData && MYYUV_E_JPEG_TABLES == myyuv_jpegin::kTables &&
+                  MYYUV_JPEG_SEGMENTS_MIN == myyuv_jpegin::kSegThreshold,
+              "jpeg_import.h's codes are the header's");
+namespace {
+
+// The smallest q in 1..100 whose make_qtable is `t` (natural order), or 0.
+uint8_t keep_quality(const uint8_t t[64], bool chroma) {
+  for (int q = 1; q <= 100; q++) {
+    float f[64];
+    make_qtable(q, chroma, f);
+    int i = 0;
+    while (i < 64 && f[i] == (float)t[i]) i++;
+    if (i == 64) return (uint8_t)q;
+  }
+  return 0;
+}
+
+// A parsed file: inspect's findings, the segment table, the qualities the
+// stream is decoded with and the call's rescale tables (file -> destination).
+struct JpegIn {
+  myyuv_jpegin::Info I;
+  std::vector<myyuv_jpegin::Seg> segs;
+  uint8_t q[3];
+  RequantTables rq;
+  uint32_t rescale = 0;  // bit p: plane p's table is not the destination's
+  bool on_gpu = false;
+  FrameGeom G;
+};
+
+bool jpeg_on_gpu(const myyuv_jpegin::Info& I) {
+  bool ri = true;
+  for (uint32_t s = 0; s < I.plan.nscan; s++) ri = ri && I.plan.ri[s] != 0;
+  return ri && I.nseg >= myyuv_jpegin::kSegThreshold;
+}
+
+// The checks that need no device, in the header's order.
+int jpeg_parse(const uint8_t* file, uint32_t size, const uint8_t* quality, JpegIn& J) {
+  // one walk over the file for all but the longest tables: room for 64 Ki intervals first
+  J.segs.resize(1u << 16);
+  int e = myyuv_jpegin::inspect(file, size, J.I, J.segs.data(), (uint32_t)J.segs.size());
+  if (e) return e;
+  const bool again = J.I.nseg > J.segs.size();
+  J.segs.resize(J.I.nseg);
+  if (again && (e = myyuv_jpegin::inspect(file, size, J.I, J.segs.data(), J.I.nseg))) return e;
+  if (quality) {
+    if ((e = check_q(quality))) return e;
+    std::memcpy(J.q, quality, 3);
+  } else {
+    for (int p = 0; p < 3; p++)
+      if (!(J.q[p] = keep_quality(J.I.qt[p], p != 0))) return MYYUV_E_JPEG_TABLES;
+  }
+  for (int p = 0; p < 3; p++) {
+    for (int i = 0; i < 64; i++) J.rq.qs[p][i] = (float)J.I.qt[p][i];
+    make_qtable(J.q[p], p != 0, J.rq.qd[p]);
+    if (std::memcmp(J.rq.qs[p], J.rq.qd[p], sizeof(J.rq.qs[p])) != 0) J.rescale |= 1u << p;
+  }
+  J.on_gpu = jpeg_on_gpu(J.I);
+  return make_geom(J.I.Wp, J.I.Hp, J.G);
+}
+
+// The rescale tables of this call, on the device in stream order (a buffer of
+// their own: the requantiser's cache is keyed by qualities and stays valid).
+int jpeg_tables(myyuv_hip_ctx* c, const JpegIn& J, hipStream_t s) {
+  if (c->jrq.grow(sizeof(RequantTables))) return MYYUV_E_HIP;
+  return h2d(c->jrq.p, &J.rq, sizeof(RequantTables), s);
+}
+
+// The restart-interval path: the file at d_file -> the stream at d_out.
+int launch_jpeg_import(myyuv_hip_ctx* c, const JpegIn& J, const void* d_file, void* d_out, uint32_t cap_out,
+                       uint32_t* d_size_out, hipStream_t s) {
+  using namespace myyuv_jpegin;
+  const Plan& P = J.I.plan;
+  const uint32_t nseg = J.I.nseg, nblk = J.G.cum[3];
+  if (c->jseg.grow((size_t)nseg * sizeof(Seg)) || c->jtab.grow(6 * sizeof(DecTab))) return MYYUV_E_HIP;
+  DecTab tabs[6];
+  for (int p = 0; p < 3; p++) {
+    tabs[p] = J.I.dc[p];
+    tabs[3 + p] = J.I.ac[p];
+  }
+  int e = h2d(c->jseg.p, J.segs.data(), (size_t)nseg * sizeof(Seg), s);
+  e |= h2d(c->jtab.p, tabs, sizeof(tabs), s);
+  e |= hipMemsetAsync(c->work.p, 0, 4, s) != hipSuccess;
+  // blocks of the padded grid that no scan holds are all-zero blocks
+  if (P.ns[0] == 1 && (P.cw[0] != P.bw[0] || P.ch[0] * 8 != J.I.Hp)) {
+    e |= hipMemsetAsync(c->rmask.p, 0, nblk, s) != hipSuccess;
+    e |= hipMemsetAsync(c->binfo.p, 0, (size_t)nblk * 4, s) != hipSuccess;
+  }
+  e |= launch(c, MYYUV_K_JPEG_IMPORT, k_jpeg_import, dim3(ceil_div(nseg, kWave)), dim3(kWave), s,
+              static_cast<const uint32_t*>(d_file), c->jseg.as<const Seg>(), nseg, P, c->jtab.as<const DecTab>(),
+              c->jrq.as<const RequantTables>(), J.rescale, c->coef.as<uint4>(), c->rmask.as<uint8_t>(),
+              c->binfo.as<uint32_t>(), c->err.as<unsigned long long>());
+  e |= launch_encode_tail(c, J.G, d_out, cap_out, d_size_out, s);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+// The coefficient-image path: img (int16 [blocks][64]) on the device -> the stream.
+int launch_jpeg_import_coef(myyuv_hip_ctx* c, const JpegIn& J, const void* d_img, void* d_out, uint32_t cap_out,
+                            uint32_t* d_size_out, hipStream_t s) {
+  const FrameGeom& G = J.G;
+  int e = hipMemsetAsync(c->work.p, 0, 4, s) != hipSuccess;
+  e |= launch(c, MYYUV_K_JPEG_IMPORT_COEF, k_jpeg_import_coef, dim3(ceil_div(G.cum[3], kWave)), dim3(kWave), s,
+              static_cast<const uint4*>(d_img), G.cum[3], G.cum[1], G.cum[2], c->jrq.as<const RequantTables>(),
+              J.rescale, c->coef.as<uint4>(), c->rmask.as<uint8_t>(), c->binfo.as<uint32_t>());
+  e |= launch_encode_tail(c, G, d_out, cap_out, d_size_out, s);
+  return e ? MYYUV_E_HIP : 0;
+}
+
+}  // namespace
+
+int myyuv_jpeg_inspect(const uint8_t* file, uint32_t size, myyuv_jpeg_info* info) {
+  if (!file || !info) return MYYUV_E_ARG;
+  std::memset(info, 0, sizeof(*info));
+  auto I = std::make_unique<myyuv_jpegin::Info>();
+  if (int e = myyuv_jpegin::inspect(file, size, *I, nullptr, 0)) return e;
+  info->width = I->W;
+  info->height = I->H;
+  info->padded_width = I->Wp;
+  info->padded_height = I->Hp;
+  info->scans = I->plan.nscan;
+  for (uint32_t s = 0; s < I->plan.nscan; s++) info->restart_interval[s] = I->plan.ri[s];
+  info->segments = I->nseg;
+  info->on_gpu = jpeg_on_gpu(*I) ? 1u : 0u;
+  FrameGeom G;
+  info->payload_bound = make_geom(I->Wp, I->Hp, G) ? 0u : myyuv_dct_payload_bound(I->Wp, I->Hp);
+  for (int p = 0; p < 3; p++) info->keep_quality[p] = keep_quality(I->qt[p], p != 0);
+  return 0;
+}
+
+int myyuv_gpu_jpeg_to_dct(myyuv_hip_handle c, const uint8_t* file, uint32_t size, const uint8_t* quality,
+                          uint8_t* out, uint32_t cap, uint32_t* out_size, uint32_t* width, uint32_t* height,
+                          uint8_t q_out[3], int64_t* bad_block) {
+  if (bad_block) *bad_block = -1;
+  if (!c || !file || !out || !out_size || !width || !height || !q_out) return MYYUV_E_ARG;
+  auto J = std::make_unique<JpegIn>();
+  int e = jpeg_parse(file, size, quality, *J);
+  if (e) return e;
+  const FrameGeom& G = J->G;
+  *width = J->I.Wp;
+  *height = J->I.Hp;
+  std::memcpy(q_out, J->q, 3);
+  std::vector<int16_t> img;
+  if (!J->on_gpu) {  // the host decode, by the kernel's own block decoder
+    img.assign((size_t)G.cum[3] * 64, 0);
+    int64_t bad = -1;
+    if ((e = myyuv_jpegin::decode_scans(file, size, J->I, J->segs.data(), J->I.nseg, img.data(), &bad))) {
+      if (bad_block) *bad_block = bad;
+      return e;
+    }
+  }
+  Entry en(c);
+  hipStream_t s = en.s;
+  // the device writes into a buffer of the bound's size, so a result larger
+  // than the caller's `cap` is known by its size alone (as compress)
+  const uint32_t bound = myyuv_dct_payload_bound(J->I.Wp, J->I.Hp);
+  const size_t nin = J->on_gpu ? ((size_t)size + 3) & ~(size_t)3 : img.size() * 2;
+  if ((e = reserve(c, G))) return e;
+  if (c->jin.grow(nin) || c->payload.grow(bound) || c->psize.grow(8)) return MYYUV_E_HIP;
+  uint32_t* psz = c->psize.as<uint32_t>();
+  if (reset_err(c, s) || (e = jpeg_tables(c, *J, s))) return MYYUV_E_HIP;
+  if (J->on_gpu) {
+    if (hipMemsetAsync(static_cast<uint8_t*>(c->jin.p) + (nin - 4), 0, 4, s) != hipSuccess ||
+        h2d(c->jin.p, file, size, s))
+      return MYYUV_E_HIP;
+    e = launch_jpeg_import(c, *J, c->jin.p, c->payload.p, bound, psz + 1, s);
+  } else {
+    if (h2d(c->jin.p, img.data(), nin, s)) return MYYUV_E_HIP;
+    e = launch_jpeg_import_coef(c, *J, c->jin.p, c->payload.p, bound, psz + 1, s);
+  }
+  if (e) return e;
+  uint32_t nout = 0;
+  if (hipMemcpyAsync(&nout, psz + 1, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return MYYUV_E_HIP;
+  if ((e = read_err(c, s, bad_block))) {  // (synchronises)
+    (void)reset_err(c, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  *out_size = nout;
+  if (nout > cap) return MYYUV_E_CAPACITY;
+  if (d2h(out, c->payload.p, nout, s)) return MYYUV_E_HIP;
+  if (c->prof) drain_profile(c);
+  return 0;
+}
+
+int myyuv_gpu_jpeg_to_dct_device(myyuv_hip_handle c, const void* d_file, const uint8_t* file, uint32_t size,
+                                 const uint8_t* quality, void* d_out, uint32_t cap, uint32_t* d_out_size,
+                                 uint32_t* width, uint32_t* height, uint8_t q_out[3], void* stream) {
+  if (!c || !d_file || !file || !d_out || !d_out_size || !width || !height || !q_out) return MYYUV_E_ARG;
+  if (((uintptr_t)d_file & 3) || ((uintptr_t)d_out & 3)) return MYYUV_E_ARG;
+  auto J = std::make_unique<JpegIn>();
+  int e = jpeg_parse(file, size, quality, *J);
+  if (e) return e;
+  if (!J->on_gpu) return MYYUV_E_JPEG_UNSUPPORTED;
+  *width = J->I.Wp;
+  *height = J->I.Hp;
+  std::memcpy(q_out, J->q, 3);
+  Entry en(c, stream);
+  if ((e = reserve(c, J->G)) || (e = jpeg_tables(c, *J, en.s))) return e;
+  return launch_jpeg_import(c, *J, d_file, d_out, cap, d_out_size, en.s);
+}
+
 // ---- downscale (defined in myyuv_hip.h) -------------------------------------
 int myyuv_gpu_dct_downscale(myyuv_hip_handle c, const uint8_t* payload, uint32_t size, uint32_t w, uint32_t h,
                             const uint8_t q_src[3], uint32_t denom, const uint8_t q_dst[3], uint8_t* out,
@@ -2899,7 +3111,7 @@ int myyuv_gpu_dct_decompress_to_bmp_frames(myyuv_hip_handle c, const uint8_t* co
 }
 
 int myyuv_hip_profile(myyuv_hip_handle c, int enable) {
-  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_MAX) - 1u : 0u);
+  return myyuv_hip_profile_kernels(c, enable ? (1u << MYYUV_K_CEIL) - 1u : 0u);
 }
 
 int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
@@ -2908,8 +3120,8 @@ int myyuv_hip_profile_kernels(myyuv_hip_handle c, uint32_t mask) {
   DeviceGuard g(c->device);
   (void)hipStreamSynchronize(c->stream);
   drain_profile(c);
-  c->prof = mask & ((1u << MYYUV_K_MAX) - 1u);
-  for (int k = 0; k < MYYUV_K_MAX; k++) {
+  c->prof = mask & ((1u << MYYUV_K_CEIL) - 1u);
+  for (int k = 0; k < MYYUV_K_CEIL; k++) {
     c->ms[k] = 0;
     c->launches[k] = 0;
   }
@@ -2922,8 +3134,8 @@ int myyuv_hip_kernel_stats_n(myyuv_hip_handle c, uint32_t n, double* ms, int64_t
   DeviceGuard g(c->device);
   drain_profile(c);
   for (uint32_t k = 0; k < n; k++) {
-    ms[k] = k < MYYUV_K_MAX ? c->ms[k] : 0.0;
-    launches[k] = k < MYYUV_K_MAX ? c->launches[k] : 0;
+    ms[k] = k < MYYUV_K_CEIL ? c->ms[k] : 0.0;
+    launches[k] = k < MYYUV_K_CEIL ? c->launches[k] : 0;
   }
   return 0;
 }

@@ -53,9 +53,18 @@ K_TOP = len(KERNELS_TOP)  # MYYUV_K_TOP: frozen like the bounds before it; the i
 KERNELS_MAX = KERNELS_TOP + ["jpeg_export", "jpeg_place"]
 K_JPEG = KERNELS_MAX.index("jpeg_export")
 K_JPEG_PLACE = KERNELS_MAX.index("jpeg_place")
-K_MAX = len(KERNELS_MAX)  # MYYUV_K_MAX
+K_MAX = len(KERNELS_MAX)  # MYYUV_K_MAX: frozen like the bounds before it; the ids after it end at K_CEIL
+# the JPEG import's ids follow; Codec.profile / Codec.kernel_stats take and return KERNELS_CEIL's names
+KERNELS_CEIL = KERNELS_MAX + ["jpeg_import", "jpeg_import_coef"]
+K_JPEG_IMPORT = KERNELS_CEIL.index("jpeg_import")
+K_JPEG_IMPORT_COEF = KERNELS_CEIL.index("jpeg_import_coef")
+K_CEIL = len(KERNELS_CEIL)  # MYYUV_K_CEIL
 E_TARGET = 18  # MYYUV_E_TARGET: "target not reachable" (error_message; strerror's table ends at 17)
 E_JPEG_DIM = 20  # MYYUV_E_JPEG_DIM: "JPEG width and height must not exceed 65535" (error_message)
+# the JPEG import's (error_message): not a file the container can hold, a damaged file, damaged
+# entropy data (with the failing block), tables that are no quality's
+E_JPEG_UNSUPPORTED, E_JPEG_SYNTAX, E_JPEG_DATA, E_JPEG_TABLES = 21, 22, 23, 24
+JPEG_SEGMENTS_MIN = 64  # MYYUV_JPEG_SEGMENTS_MIN
 PROBE_SIZE, PROBE_METRIC = 1, 2  # MYYUV_PROBE_*
 # myyuv_block_metric, as the maps of the compare calls come back
 BLOCK_METRIC = np.dtype([("sse", np.uint32), ("ssim", np.int32)])
@@ -97,6 +106,7 @@ EXPORTS = [
     "myyuv_gpu_dct_compress_to_size_device", "myyuv_gpu_dct_compress_to_sse_device",
     "myyuv_gpu_bmp_dct_compress", "myyuv_gpu_bmp_dct_compress_device",
     "myyuv_jpeg_bound", "myyuv_gpu_dct_to_jpeg", "myyuv_gpu_dct_to_jpeg_device", "myyuv_gpu_iyuv_to_jpeg",
+    "myyuv_jpeg_inspect", "myyuv_gpu_jpeg_to_dct", "myyuv_gpu_jpeg_to_dct_device",
 ]
 
 
@@ -142,6 +152,22 @@ PROBE_DTYPE = np.dtype([("plane_bytes", np.uint32, 3), ("payload_bytes", np.uint
 _lib = None
 # myyuv_payload_alloc_fn
 PAYLOAD_ALLOC = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32)
+
+
+class JpegInfo(ctypes.Structure):
+    """myyuv_jpeg_info."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("padded_width", ctypes.c_uint32),
+                ("padded_height", ctypes.c_uint32), ("scans", ctypes.c_uint32),
+                ("restart_interval", ctypes.c_uint32 * 3), ("segments", ctypes.c_uint32),
+                ("on_gpu", ctypes.c_uint32), ("payload_bound", ctypes.c_uint32),
+                ("keep_quality", ctypes.c_uint8 * 3), ("reserved", ctypes.c_uint8)]
+
+    def as_dict(self):
+        return {"width": self.width, "height": self.height, "padded_width": self.padded_width,
+                "padded_height": self.padded_height, "scans": self.scans,
+                "restart_interval": list(self.restart_interval)[:self.scans], "segments": self.segments,
+                "on_gpu": bool(self.on_gpu), "payload_bound": self.payload_bound,
+                "keep_quality": tuple(self.keep_quality)}
 
 
 class CodecError(RuntimeError):
@@ -272,6 +298,10 @@ def load():
     L.myyuv_gpu_dct_to_jpeg.argtypes = [vp, u8p, u32, u32, u32, u8p, u8p, u32, ctypes.POINTER(u32), i64p]
     L.myyuv_gpu_dct_to_jpeg_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, u8p, vp, u32, vp, vp]
     L.myyuv_gpu_iyuv_to_jpeg.argtypes = [vp, u8p, u32, u32, u8p, u8p, u32, ctypes.POINTER(u32)]
+    u32p = ctypes.POINTER(u32)
+    L.myyuv_jpeg_inspect.argtypes = [u8p, u32, ctypes.POINTER(JpegInfo)]
+    L.myyuv_gpu_jpeg_to_dct.argtypes = [vp, u8p, u32, u8p, u8p, u32, u32p, u32p, u32p, u8p, i64p]
+    L.myyuv_gpu_jpeg_to_dct_device.argtypes = [vp, vp, u8p, u32, u8p, vp, u32, vp, u32p, u32p, u8p, vp]
     L.myyuv_debug_tinfo_guard.argtypes =[vp, u32, ctypes.c_int, ctypes.POINTER(u32)]  # diagnostic
     L.myyuv_debug_huff_encode_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), u32, u32, u8p, u8p,
                                                  ctypes.POINTER(u32)]  # diagnostic
@@ -293,6 +323,17 @@ def error_message(code):
 
 def payload_bound(w, h):
     return load().myyuv_dct_payload_bound(w, h)
+
+
+def jpeg_inspect(data):
+    """myyuv_jpeg_inspect (no device): a JPEG file's sizes, layout and, per
+    plane, the quality an import that keeps the file's tables would take."""
+    src = np.ascontiguousarray(np.frombuffer(memoryview(data).cast("B"), np.uint8))
+    info = JpegInfo()
+    rc = load().myyuv_jpeg_inspect(_u8(src), src.nbytes, ctypes.byref(info))
+    if rc:
+        raise CodecError(rc)
+    return info.as_dict()
 
 
 def jpeg_bound(w, h):
@@ -953,6 +994,52 @@ class Codec:
         if rc:
             raise CodecError(rc)
 
+    # -- import from JPEG: a baseline 4:2:0 JPEG file read into a DCT stream on its
+    # coefficients (defined in include/myyuv_hip.h) --
+    def from_jpeg(self, data, q=None):
+        """JPEG file -> (payload, Wp, Hp, qualities).  q None keeps the file's
+        tables (E_JPEG_TABLES when they are no quality's), else the stream is
+        rescaled to q."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(data).cast("B"), np.uint8))
+        bound = jpeg_inspect(src)["payload_bound"]
+        out = np.empty(max(bound, 64), np.uint8)
+        n, w, h, qs = self.from_jpeg_into(src, out, q)
+        return out[:n].tobytes(), w, h, qs
+
+    def from_jpeg_into(self, data, out, q=None):
+        """from_jpeg from / into the caller's C-contiguous uint8 arrays; returns
+        (size, Wp, Hp, qualities).  A short `out` fails with E_CAPACITY, the
+        error's .size the size needed."""
+        src = _u8_array(data, "data")
+        dst = _u8_array(out, "out", writable=True)
+        size, w, h = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        qs = np.zeros(3, np.uint8)
+        bad = ctypes.c_int64(-1)
+        rc = load().myyuv_gpu_jpeg_to_dct(self._h, _u8(src), src.nbytes, None if q is None else _u8(_q(q)),
+                                          _u8(dst), dst.nbytes, ctypes.byref(size), ctypes.byref(w),
+                                          ctypes.byref(h), _u8(qs), ctypes.byref(bad))
+        if rc:
+            e = CodecError(rc, bad.value)
+            e.size = size.value
+            raise e
+        return size.value, w.value, h.value, tuple(int(v) for v in qs)
+
+    def from_jpeg_device(self, d_file, data, d_out, cap, d_out_size, q=None, stream=None):
+        """Device-resident: the file at d_file (and the same bytes, `data`, on
+        the host) -> the stream at d_out, its size at d_out_size (device u32);
+        asynchronous, data errors through sync_status.  Returns (Wp, Hp,
+        qualities).  Files below JPEG_SEGMENTS_MIN restart intervals:
+        E_JPEG_UNSUPPORTED."""
+        src = np.ascontiguousarray(np.frombuffer(memoryview(data).cast("B"), np.uint8))
+        w, h = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        qs = np.zeros(3, np.uint8)
+        rc = load().myyuv_gpu_jpeg_to_dct_device(self._h, d_file, _u8(src), src.nbytes,
+                                                 None if q is None else _u8(_q(q)), d_out, cap, d_out_size,
+                                                 ctypes.byref(w), ctypes.byref(h), _u8(qs), stream)
+        if rc:
+            raise CodecError(rc)
+        return w.value, h.value, tuple(int(v) for v in qs)
+
     # -- transform: a DCT stream mirrored, rotated or transposed on its coefficients,
     # optionally at another quality (defined in include/myyuv_hip.h) --
     def transform(self, payload, w, h, q_src, op, q_dst=None):
@@ -1146,19 +1233,19 @@ class Codec:
         if kernels is None:
             rc = load().myyuv_hip_profile(self._h, 1 if enable else 0)
         else:
-            mask = sum(1 << KERNELS_MAX.index(k) for k in kernels) if enable else 0
+            mask = sum(1 << KERNELS_CEIL.index(k) for k in kernels) if enable else 0
             rc = load().myyuv_hip_profile_kernels(self._h, mask)
         if rc:
             raise CodecError(rc)
 
     def kernel_stats(self):
-        """{name: (summed ms, launches)} for every name of KERNELS_MAX."""
-        ms = (ctypes.c_double * K_MAX)()
-        n = (ctypes.c_int64 * K_MAX)()
-        rc = load().myyuv_hip_kernel_stats_n(self._h, K_MAX, ms, n)
+        """{name: (summed ms, launches)} for every name of KERNELS_CEIL."""
+        ms = (ctypes.c_double * K_CEIL)()
+        n = (ctypes.c_int64 * K_CEIL)()
+        rc = load().myyuv_hip_kernel_stats_n(self._h, K_CEIL, ms, n)
         if rc:
             raise CodecError(rc)
-        return {KERNELS_MAX[i]: (ms[i], n[i]) for i in range(K_MAX)}
+        return {KERNELS_CEIL[i]: (ms[i], n[i]) for i in range(K_CEIL)}
 
     def tinfo_guard(self, ntiles, arm):
         """Diagnostic (not in include/myyuv_hip.h): arm=True writes a canary
